@@ -2,6 +2,7 @@
 """Benchmark: particles redistributed/sec (whole node), HBM / xGMI roofline.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--soa]
+                  [--full] [--dump-outputs DIR]
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...,
          or bare `python bench.py --gpus N`: with no WORLD_SIZE in the
          environment the script starts its N rank processes itself (children,
@@ -21,9 +22,17 @@ already resident in HBM (SURVEY §8d generator, generated on the device):
 
 Rank 0 prints ONE JSON line.  ``roofline`` is the dominant kernel's
 algorithmic bytes per launch over its average launch
-time, measured with HIP events on its own stream during the timed steps;
-``cpu_baseline`` times the NumPy restatement of the reference algorithm
-(oracle/, the checker) on a bounded sample on this host's cores (N=1 only).
+time, measured with HIP events on its own stream during the timed steps.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+``--dump-outputs DIR`` then writes what the last timed step returned (and the
+positions it wrapped) as DIR/<name>.npy: the inputs are seeded, so two builds
+can be compared array by array.  ``--full`` adds everything that takes runs
+of its own (their keys are null in a plain line): ``cpu_baseline*`` time the
+NumPy / C restatements of the reference algorithm (oracle/, the checker) on a
+bounded sample on this host's cores (N=1 only); the kernels not timed inside
+the region get an untimed detail pass; ``count_skew``, ``onepass``; at N > 1
+``xgmi``, ``rccl``, ``exchange_ab`` and ``n1_same_workload_ms``.
 """
 from __future__ import annotations
 
@@ -307,6 +316,74 @@ def load_traffic(kernel, workload):
         return None
 
 
+# --dump-outputs: the record layouts of the synthetic payloads (synth_uniform /
+# synth_clustered: [x, y, z f64, id i64]; synth_wide: [pos f32 x3, vel f32 x3,
+# mass f32, id i64]) and the rows sampled from an output longer than that
+REC32 = np.dtype([("xyz", "<f8", 3), ("id", "<i8")])
+REC36 = np.dtype([("pos", "<f4", 3), ("vel", "<f4", 3), ("mass", "<f4"), ("id", "<i8")])
+F32X3, F32, F64X3, I64 = (np.dtype([("v", t, k)]) for t, k in
+                          (("<f4", 3), ("<f4", 1), ("<f8", 3), ("<i8", 1)))
+DUMP_SAMPLE_ROWS = 1 << 16
+DUMP_MAX_BYTES = 64 << 20
+
+
+def received_outputs(res, prefix="received"):
+    """redistribute_by_position's return value (an array, a tuple of SoA
+    fields, or (data, offsets) with fine cells) as dump_outputs entries; the
+    (m, 32) / (m, 36) uint8 record arrays of this bench are decoded by field."""
+    if isinstance(res, (tuple, list)):
+        return [e for i, r in enumerate(res) for e in received_outputs(r, f"{prefix}{i}")]
+    if res is None:
+        return []
+    t = torch.as_tensor(res)
+    rec = {32: REC32, 36: REC36}.get(t.shape[-1]) if t.dtype == torch.uint8 and t.dim() == 2 else None
+    return [(prefix, t, rec, None)]
+
+
+def dump_outputs(dirname, entries, suffix=""):
+    """Write what the last timed step returned as ``dirname/<name>.npy``
+    (float64; float32 stays float32).  ``entries``: (name, tensor, layout,
+    regions) -- ``layout`` None for a numeric tensor, else the structured
+    dtype of the rows of a uint8 buffer; ``regions`` None, or (counts,
+    cap) for an output kept as per-bin regions of cap rows, of which the first
+    counts[b] are rows of bin b.  An output of more than DUMP_SAMPLE_ROWS rows
+    is written as a fixed sample of its rows (seeded by the row count alone),
+    in row order; the total stays below DUMP_MAX_BYTES."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t, layout, regions in entries:
+        if layout is not None:
+            t = t.reshape(-1).view(torch.uint8)
+            t = t[:t.numel() // layout.itemsize * layout.itemsize].view(-1, layout.itemsize)
+        if regions is not None:
+            # a bin that did not fit (count > cap, or -1) has at most cap rows there
+            cnt = np.clip(regions[0].cpu().numpy().astype(np.int64), 0, int(regions[1]))
+            off = np.concatenate([[0], np.cumsum(cnt)])
+            rows = int(off[-1])
+        else:
+            rows = int(t.shape[0]) if t.dim() else 1
+        idx = None
+        if rows > DUMP_SAMPLE_ROWS:
+            idx = np.unique(np.random.default_rng(SEED + rows).integers(0, rows, DUMP_SAMPLE_ROWS))
+        elif regions is not None:
+            idx = np.arange(rows)
+        if idx is not None:
+            if regions is not None:   # row j of the bins laid end to end -> its region's row
+                b = np.searchsorted(off, idx, side="right") - 1
+                idx = b * int(regions[1]) + (idx - off[b])
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        if layout is not None:
+            a = np.ascontiguousarray(a).view(layout).reshape(-1)
+            a = np.hstack([a[nm].reshape(a.shape[0], -1).astype(np.float64)
+                           for nm in layout.names])
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+
+
 def _free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
         so.bind(("127.0.0.1", 0))
@@ -392,7 +469,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--particles", "--n", dest="n", type=int, default=0,
                     help="particles per GPU (default: config size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the CPU baselines (N = 1), the untimed detail "
+                         "pass of the kernels not timed inside the region, count skew, the "
+                         "one-pass region check, and at N > 1 the xGMI figures, the RCCL facts, "
+                         "the one-message exchange and the same workload at N = 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned as "
+                         "DIR/<name>.npy (float64 / float32; long outputs as a fixed sample of "
+                         "their rows, below 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines")
     ap.add_argument("--prof", choices=("report", "all", "none"), default="report",
                     help="kernels timed with HIP events inside the timed region: report = "
                          "pack (+ exchange) only, all, none")
@@ -434,9 +521,10 @@ def main():
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE {world}"
     # CPU baseline first: its rank processes are spawned before this process
     # touches the GPU
-    cpu = cpu_baseline() if (world == 1 and not args.no_cpu_baseline) else None
-    cpu_1 = cpu_baseline_cfg1() if (world == 1 and not args.no_cpu_baseline) else None
-    cpu_c = cpu_baseline_c() if (world == 1 and not args.no_cpu_baseline) else None
+    with_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    cpu = cpu_baseline() if with_cpu else None
+    cpu_1 = cpu_baseline_cfg1() if with_cpu else None
+    cpu_c = cpu_baseline_c() if with_cpu else None
     if os.environ.get("MGR_BENCH_SHARED_GPU") == "1":
         # rehearsal of the N>1 path on a 1-GPU box: every rank on GPU 0, each
         # its own RCCL "host" (socket transport) -- numbers are not xGMI ones
@@ -446,7 +534,7 @@ def main():
     torch.cuda.set_device(local)
     dist = None
     multi = world > 1 or args.exchange
-    rccl_log = rccl_log_env(os.environ) if world > 1 else None
+    rccl_log = rccl_log_env(os.environ) if (world > 1 and args.full) else None
     if multi:
         import torch.distributed as dist
         if world == 1:   # --exchange without a launcher: a one-rank group
@@ -483,8 +571,17 @@ def main():
             recv_fids = recv_fids.clone()
 
             def step():
-                part.partition_fields_device(flats, rbs, src[0], fine_cells=[8, 8, 8])
-                R1.fine_cell_sort(rcv, rcv[0], [8, 8, 8], fine_ids=recv_fids)
+                o = part.partition_fields_device(flats, rbs, src[0], fine_cells=[8, 8, 8])
+                return o, R1.fine_cell_sort(rcv, rcv[0], [8, 8, 8], fine_ids=recv_fids)
+
+            def outputs(res):
+                (outs, fids, cnt), (srt, off) = res
+                soa = (F32X3, F32X3, F32, I64)
+                return ([(f"send_field{i}", o, d, None) for i, (o, d) in enumerate(zip(outs, soa))]
+                        + [("send_fine_ids", fids, None, None), ("bin_counts", cnt, None, None),
+                           ("position", src[0], None, None)]
+                        + [(f"sorted_field{i}", t, None, None) for i, t in enumerate(srt)]
+                        + [("fine_offsets", off, None, None)])
         elif cfg == 5:
             # one GPU's share of config 5: 64M 36-byte records; the local stage
             # (bin + scan + pack into 8 destinations) and the destination-side
@@ -513,7 +610,15 @@ def main():
 
                 def step():
                     last["r"] = part.partition_onepass_device(flat, 36, pos, fine_cells=[8, 8, 8])
-                    R1.fine_cell_sort(recv, rpos, [8, 8, 8], fine_ids=recv_fids)
+                    return last["r"], R1.fine_cell_sort(recv, rpos, [8, 8, 8], fine_ids=recv_fids)
+
+                def outputs(res):
+                    # the send_buff regions: bin b's cnt[b] rows from row b * cap
+                    (out, fo, cnt, cap), (srt, off) = res
+                    return [("send_records", out, REC36, (cnt, cap)),
+                            ("send_fine_ids", fo, None, (cnt, cap)),
+                            ("bin_counts", cnt, None, None), ("position", pos, None, None),
+                            ("sorted_records", srt, REC36, None), ("fine_offsets", off, None, None)]
 
                 def onepass_check():
                     # every bin fit its region (a count above cap would need the
@@ -524,8 +629,14 @@ def main():
                             "fits": bool((c >= 0).all() and (c <= cap).all())}
             else:
                 def step():
-                    part.partition_device(flat, 36, pos, fine_cells=[8, 8, 8])
-                    R1.fine_cell_sort(recv, rpos, [8, 8, 8], fine_ids=recv_fids)
+                    o = part.partition_device(flat, 36, pos, fine_cells=[8, 8, 8])
+                    return o, R1.fine_cell_sort(recv, rpos, [8, 8, 8], fine_ids=recv_fids)
+
+                def outputs(res):
+                    (out, fids, cnt), (srt, off) = res
+                    return [("send_records", out, REC36, None), ("send_fine_ids", fids, None, None),
+                            ("bin_counts", cnt, None, None), ("position", pos, None, None),
+                            ("sorted_records", srt, REC36, None), ("fine_offsets", off, None, None)]
         else:
             if cfg == 4:
                 workload = f"cfg4_{_m(n)}_clustered_2x2x2_local_partition"
@@ -542,10 +653,20 @@ def main():
                 flats = [pos.reshape(-1).view(torch.uint8), ids.view(torch.uint8)]
 
                 def step():
-                    part.partition_fields_device(flats, [24, 8], pos)
+                    return part.partition_fields_device(flats, [24, 8], pos)
+
+                def outputs(res):
+                    outs, cnt = res
+                    return [("send_field0", outs[0], F64X3, None), ("send_field1", outs[1], I64, None),
+                            ("bin_counts", cnt, None, None), ("position", pos, None, None)]
             else:
                 def step():
-                    part.partition_device(flat, 32, pos)
+                    return part.partition_device(flat, 32, pos)
+
+                def outputs(res):
+                    out, cnt = res
+                    return [("send_records", out, REC32, None), ("bin_counts", cnt, None, None),
+                            ("position", pos, None, None)]
     else:
         n = args.n or (N_CFG5_PER_GPU if cfg == 5 else N_CFG3_PER_GPU)
         comm = mgr.RcclComm.from_torch_distributed()
@@ -558,14 +679,14 @@ def main():
             soa = mgr.synth_wide_soa(n, seed=SEED, gid0=rank * n)
 
             def step_with(Rx):
-                Rx.redistribute_by_position(soa, soa[0], fine_cells=[8, 8, 8])
+                return Rx.redistribute_by_position(soa, soa[0], fine_cells=[8, 8, 8])
         elif cfg == 5:
             workload = f"cfg5_rec36_per_gpu_{_m(n)}_full_exchange_plus_fine_sort_888"
             rb, pos_desc = 36, "f32 (N,3) view into the 36-byte records, wrapped in place"
             rec, pos = mgr.synth_wide(n, seed=SEED, gid0=rank * n)
 
             def step_with(Rx):
-                Rx.redistribute_by_position(rec, pos, fine_cells=[8, 8, 8])
+                return Rx.redistribute_by_position(rec, pos, fine_cells=[8, 8, 8])
         else:
             if cfg == 4:
                 workload = f"cfg4_clustered_per_gpu_{_m(n)}_full_exchange"
@@ -586,13 +707,18 @@ def main():
                 del rec
 
                 def step_with(Rx):
-                    Rx.redistribute_by_position(soa, pos)
+                    return Rx.redistribute_by_position(soa, pos)
             else:
                 def step_with(Rx):
-                    Rx.redistribute_by_position(rec, pos, overload_lengths=ol)
+                    return Rx.redistribute_by_position(rec, pos, overload_lengths=ol)
 
         def step():
-            step_with(R)
+            return step_with(R)
+
+        def outputs(res):
+            # what redistribute_by_position returned (the received rows; with
+            # fine cells their offsets too) and the positions it wrapped
+            return received_outputs(res) + [("position", soa[0] if args.soa else pos, None, None)]
 
     # Fresh f64 input needs the in-place wrap written back (redist.py:68: x + L
     # rounds, so most in-box coordinates change on the first call).  The bin
@@ -618,7 +744,7 @@ def main():
     # HIP events go only around the dominant kernel (pack) and the RCCL
     # exchange inside the timed region: every timed launch adds two event
     # records to the stream (measured ~2-3 us of step time per kernel).  The
-    # other kernels are timed in an untimed detail pass after the region.
+    # other kernels are timed in an untimed detail pass after the region (--full).
     timed = {"report": ["pack", "exchange", "halo", "halo_pack", "pack_fine", "onepass"],
              "all": list(_lib.PROFILE_KERNELS),
              "none": []}[args.prof]
@@ -628,8 +754,10 @@ def main():
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()
+    res = None
     for _ in range(args.steps):
-        step()
+        res = None          # no step's results outlive it, but the last one's
+        res = step()
     ev1.record()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -639,6 +767,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and res is not None:
+        # every rank writes its own arrays: rank 0 <name>.npy, rank r <name>.rank<r>.npy
+        dump_outputs(args.dump_outputs, outputs(res), f".rank{rank}" if rank else "")
+    del res
 
     kernels = {}
     for k in _lib.PROFILE_KERNELS:
@@ -651,7 +783,7 @@ def main():
     missing = [k for k in list(row_bytes_per_kernel(cfg, bool(args.overload > 0),
                                                     soa=args.soa, onepass=onepass)) + ["scan"]
                if k not in kernels]
-    if missing:
+    if missing and args.full:
         # detail pass (not timed): the kernels left out of the timed region
         _lib.profile_reset()
         _lib.profile_select(missing)
@@ -665,25 +797,25 @@ def main():
             if cnt:
                 kernels[k] = {"avg_ms": ms / cnt, "launches": cnt, "in_timed_region": False}
     _lib.profile_select(None)
-    onepass_info = onepass_check() if onepass else None
+    onepass_info = onepass_check() if (onepass and args.full) else None
     # the count matrix's max/mean (load imbalance of the
     # redistribution: rows each destination receives, max over mean) -- the
     # N=1 line's 1 x 8 row of virtual destinations, or the N>1 ranks' count rows
     # gathered after the timed region
     skew = None
-    if not multi and cfg in (2, 4):
+    if args.full and not multi and cfg in (2, 4):
         skew = count_skew(part.last_counts.cpu().numpy().reshape(1, -1))
-    elif multi:
+    elif args.full and multi:
         sc = torch.as_tensor(R.last_counts[0], dtype=torch.int64, device="cuda")
         rows = [torch.empty_like(sc) for _ in range(world)] if world > 1 else [sc]
         if world > 1:
             dist.all_gather(rows, sc)
         skew = count_skew(torch.stack(rows).cpu().numpy())
     xgmi = None
-    if multi and "exchange" in kernels:
+    if args.full and multi and "exchange" in kernels:
         xgmi = xgmi_report(R.last_traffic, kernels["exchange"], dist, world, chunks)
     rccl, exchange_ab, n1_same_ms = None, None, None
-    if multi and world > 1:
+    if args.full and multi and world > 1:
         # untimed: one message per peer (exchange_chunks = 1) on the same
         # inputs, beside the pipelined steps of the timed region
         R.exchange_chunks = 1

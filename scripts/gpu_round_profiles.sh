@@ -17,7 +17,7 @@ IFS='|' read -ra CFGS <<< "$(echo "$LINESET" | sed -E 's/ (cfg[0-9a-z]*::|halo::
 for cfg in "${CFGS[@]}"; do
   name=${cfg%%::*}; args=${cfg#*::}
   run ${name}_trace rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$PROF/${name}_trace -o run \
-    -- python3 $R/bench.py --no-cpu-baseline $args --steps 20 --warmup 5 || exit 1
+    -- python3 $R/bench.py --full --no-cpu-baseline $args --steps 20 --warmup 5 || exit 1
   for c in FETCH_SIZE WRITE_SIZE; do
     run ${name}_${c} rocprofv3 --pmc $c --output-format csv -d $R/gpurun_out/$PROF/${name}_${c} -o pmc \
       -- python3 $R/bench.py --no-cpu-baseline --prof none $args --steps 3 --warmup 1 || exit 1

@@ -69,6 +69,59 @@ def test_no_json_line_is_a_failure(child):
     assert bench.launch_ranks(2, ["silent"], 60, script=child, out=io.StringIO()) == 3
 
 
+def test_dump_outputs_layouts_regions_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: records decoded by field, per-bin regions
+    laid end to end (rows past a bin's count never read), numeric tensors as
+    float64, long outputs as the same sample of rows on every call."""
+    import numpy as np
+    import torch
+
+    n = 11
+    rec = np.zeros(n, dtype=bench.REC32)
+    rec["xyz"] = np.arange(3 * n, dtype=np.float64).reshape(n, 3) / 7
+    rec["id"] = np.arange(n) + (1 << 40)
+    flat = torch.from_numpy(rec.view(np.uint8).copy())
+    # regions of cap 4 rows: bins of 3, 0 and 2 rows, the rest never written
+    cnt, cap = torch.tensor([3, 0, 2]), 4
+    reg = torch.full((3 * cap, 36), 255, dtype=torch.uint8)
+    r36 = np.zeros(5, dtype=bench.REC36)
+    r36["pos"] = np.arange(15, dtype=np.float32).reshape(5, 3)
+    r36["mass"], r36["id"] = 1.0, np.arange(5) * 3
+    rows = torch.from_numpy(r36.view(np.uint8).reshape(5, 36).copy())
+    reg[0:3], reg[8:10] = rows[0:3], rows[3:5]
+    fo = torch.full((3 * cap,), -1, dtype=torch.int16)
+    fo[0:3], fo[8:10] = torch.tensor([5, 6, 7], dtype=torch.int16), torch.tensor(
+        [8, 9], dtype=torch.int16)
+    pos32 = torch.arange(6, dtype=torch.float32).reshape(2, 3)
+    d = str(tmp_path / "o")
+    bench.dump_outputs(d, [("rec", flat, bench.REC32, None), ("reg", reg.reshape(-1), bench.REC36,
+                                                               (cnt, cap)),
+                           ("fo", fo, None, (cnt, cap)), ("cnt", cnt, None, None),
+                           ("pos", pos32, None, None), ("f", flat[:24], bench.F64X3, None)])
+    a = np.load(os.path.join(d, "rec.npy"))
+    assert a.dtype == np.float64 and a.shape == (n, 4)
+    assert np.array_equal(a[:, :3], rec["xyz"]) and np.array_equal(a[:, 3], rec["id"])
+    g = np.load(os.path.join(d, "reg.npy"))
+    assert g.shape == (5, 8) and np.array_equal(g[:, :3], r36["pos"])
+    assert np.array_equal(g[:, 7], r36["id"]) and np.array_equal(g[:, 6], np.ones(5))
+    assert np.array_equal(np.load(os.path.join(d, "fo.npy")), [5, 6, 7, 8, 9])
+    assert np.array_equal(np.load(os.path.join(d, "cnt.npy")), [3.0, 0.0, 2.0])
+    p = np.load(os.path.join(d, "pos.npy"))
+    assert p.dtype == np.float32 and np.array_equal(p, pos32.numpy())
+    assert np.array_equal(np.load(os.path.join(d, "f.npy")), rec["xyz"][:1])
+    # a long output: a sample of rows, in row order, the same on every call
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ROWS", 64)
+    big = torch.arange(1000, dtype=torch.int64)
+    for sub in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / sub), [("big", big, None, None)], suffix=".rank1")
+    s1, s2 = (np.load(str(tmp_path / sub / "big.rank1.npy")) for sub in ("s1", "s2"))
+    assert np.array_equal(s1, s2) and 32 < len(s1) <= 64 and np.all(np.diff(s1) > 0)
+    # the size limit is enforced, not assumed
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "s3"), [("big", big, None, None)])
+
+
 def test_cpu_baseline_c_is_repeatable():
     """bench.py's threaded C baseline reports the median of its iterations
     (no allocation or first touch inside a timed call): two runs agree within
