@@ -228,7 +228,10 @@ int mgr_pack_tiles(const void* src, int64_t row_bytes, int64_t n, const void* de
  * Fields of 4-byte-multiple rows on 16-byte aligned sources (4-byte aligned
  * outputs), <= 64 bins, move together in one launch of the multi-field
  * kernel (each destination byte read and ranked once); any other field is
- * packed on its own with the same destinations.                          */
+ * packed on its own with the same destinations.  Tail read: the multi-field
+ * kernel stages those sources in 16-byte units, so a source's last unit may
+ * READ up to 12 bytes past the array's end, inside its aligned 16-byte unit
+ * (never written, never used).                                            */
 int mgr_pack_fields(int nfields, const void* const* srcs, const int64_t* row_bytes, int64_t n,
                     const void* dest, int nbins, int drop_bin, int tile_rows,
                     const void* workspace, void* const* dsts, int redirect_bin,
@@ -287,12 +290,53 @@ int mgr_partition_by_position(const mgr_plan* plan, void* pos, int pos_dtype, in
  * partition with the classic path (mgr_bin_count with periodic = 0 re-bins
  * the stored, wrapped positions identically, S2) -- or -1 everywhere when a
  * look-back gave up (nothing written).  Workspace: mgr_onepass_workspace_bytes
- * (zeroed by the call).  MGR_EUNSUPPORTED for shapes it does not take.      */
+ * (zeroed by the call).  MGR_EUNSUPPORTED for shapes it does not take.
+ * Tail read: the records are staged in 16-byte units from the 16-byte-aligned
+ * data, so the last unit may READ up to 12 bytes past the array's end, inside
+ * its aligned 16-byte unit (never written, never used).                    */
 int64_t mgr_onepass_workspace_bytes(int64_t n, int nbins);
 int mgr_partition_onepass(const mgr_plan* plan, const mgr_plan* fine_plan, void* data,
                           int64_t row_bytes, int64_t pos_offset, int pos_dtype, int64_t n,
                           int periodic, void* out, uint16_t* fine_out, int64_t cap_rows,
                           int64_t* bin_counts, void* workspace, void* stream);
+/* mgr_partition_onepass of a SoA payload: nfields arrays sharing their n rows
+ * (srcs[f]: n rows of row_bytes[f]; e.g. config 5 as positions, velocities,
+ * masses, ids), each read ONCE, binned by the positions at byte pos_offset of
+ * field pos_field's rows (float32 / float64, three coordinates), every field
+ * scattered with one ranking and one look-back per bin and tile.
+ *   Region layout: bin b's rows of field f, in their original order, from
+ *     outs[f] + b * cap_rows * row_bytes[f]; their fine cells (fine_plan as in
+ *     mgr_bin_count_fine, else NULL) from fine_out + b * cap_rows.  Every
+ *     outs[f] holds nbins * cap_rows rows.  outs[pos_field] may be NULL:
+ *     positions that are not part of the payload are staged, wrapped and
+ *     written back, but not scattered.
+ *   Overflow: rows at or beyond cap_rows are NOT written, in any field (a
+ *     wave whose rows of a bin would reach cap_rows writes none of them);
+ *     bin_counts (int64 [nbins], device) still holds every bin's rows, so a
+ *     count above cap_rows means the caller redoes the partition with the
+ *     two-pass path (mgr_bin_count with periodic = 0 re-bins the stored,
+ *     wrapped positions identically, S2).
+ *   Failure: when any tile's look-back gave up, bin_counts is -1 for EVERY
+ *     bin (written once, by the tile that finishes last), whichever tile it
+ *     was; the outputs are then incomplete.
+ *   In-place wrap: with periodic != 0 field pos_field's positions are wrapped
+ *     in place as mgr_bin_count does (S1); no other source byte is written.
+ *   Tail read: each source array is staged in 16-byte units, so its last unit
+ *     may READ up to 12 bytes past the array's end, inside its aligned
+ *     16-byte unit (never written, never used).
+ * Workspace: mgr_onepass_workspace_bytes(n, nbins), zeroed by the call.
+ * MGR_EINVAL: a null plan / srcs / row_bytes / bin_counts, nfields outside
+ * 1..MGR_MAX_FIELDS, pos_field out of range, n or cap_rows < 0, for n > 0 a
+ * null source, workspace or output (other than the position field's), or
+ * fine_plan with a null fine_out.  MGR_EUNSUPPORTED (take the two-pass path)
+ * unless: a 3-D plan of <= 64 bins, float32 / float64 positions, <= 8 fields,
+ * every row_bytes[f] a multiple of 4 in 4..64 and their sum <= 128, sources
+ * 16-byte aligned, outputs 4-byte aligned.                                 */
+int mgr_partition_onepass_fields(const mgr_plan* plan, const mgr_plan* fine_plan, int nfields,
+                                 void* const* srcs, const int64_t* row_bytes, int pos_field,
+                                 int64_t pos_offset, int pos_dtype, int64_t n, int periodic,
+                                 void* const* outs, uint16_t* fine_out, int64_t cap_rows,
+                                 int64_t* bin_counts, void* workspace, void* stream);
 /* bin starts (int64[nbins+1], device) left in the workspace by mgr_scan.   */
 int mgr_bin_starts(int64_t n, int nbins, int tile_rows, const void* workspace,
                    const int64_t** out);

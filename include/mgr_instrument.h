@@ -32,7 +32,10 @@ extern "C" {
  * this ticket publishes its prefix poisoned: a deterministic failed scan,
  * -1 = none), "fields_kernel" (multi-field packs: 0 the product's choice,
  * 1 the per-wave LDS-image kernel, 2 the tile-image kernel, 3 the
- * cooperative kernel -- each where it takes the fields, else the next).
+ * cooperative kernel -- each where it takes the fields, else the next),
+ * "onepass_poison_tile" (mgr_partition_onepass_fields: the tile with this
+ * ticket treats its look-back as given up -- it publishes its prefix
+ * poisoned and writes no rows: a deterministic failed partition, -1 = none).
  * Each call publishes a new immutable
  * snapshot of every hook (the library's launches read one snapshot each);
  * < 0 for an unknown key or an out-of-range value.                         */
@@ -52,7 +55,8 @@ int mgr_test_pos_modes(int pos_dtype, int box_dtype, int* wrap, int* quot);
  * "synth", "halo" (mgr_halo_flags, mgr_msel_count), "bin_fine"
  * (mgr_bin_count_fine), "count_ids" (mgr_count_ids, mgr_rank_ids),
  * "pack_fine" (the 65..1024-bin and ranked packs), "pack_narrow" (rows < 4
- * bytes), "halo_pack" (mgr_msel_pack*)) or of the RCCL grouped row exchange
+ * bytes), "halo_pack" (mgr_msel_pack*), "onepass" (mgr_partition_onepass),
+ * "onepass_fields" (mgr_partition_onepass_fields)) or of the RCCL grouped row exchange
  * ("exchange").  mgr_profile_select: bit k of mask times kernel id k
  * (mgr_profile_kernel_id), default all.                                    */
 int mgr_profile_enable(int on);

@@ -63,6 +63,8 @@ SIGNATURES = {
     "mgr_bin_starts": (_I, [_I64, _I, _I, _P, ctypes.POINTER(_P)]),
     "mgr_onepass_workspace_bytes": (_I64, [_I64, _I]),
     "mgr_partition_onepass": (_I, [_P, _P, _P, _I64, _I64, _I, _I64, _I, _P, _P, _I64, _P, _P, _P]),
+    "mgr_partition_onepass_fields": (_I, [_P, _P, _I, _P, _P, _I, _I64, _I, _I64, _I, _P, _P, _I64,
+                                          _P, _P, _P]),
     "mgr_halo_flags": (_I, [_P, _I, _I64, _I64, _I, _P, _P, _P, _P]),
     "mgr_bin_count_halo": (_I, [_P, _P, _I, _I64, _I64, _I, _P, _P, _P, _P, _I, _P, _P]),
     "mgr_msel_count": (_I, [_P, _I64, _I, _P, _I, _P, _P]),
@@ -193,14 +195,14 @@ HOOK_DEFAULTS = {"tile_rounds": 0, "scan_chunk": 2048, "scan_max_chunks": 1024,
                  "scan_spins": 1 << 24, "pack_img_all": 0, "rank_rows": 0, "bin_unstaged": 0,
                  "bin_generic": 0, "pack_generic": 0, "scan_delay_bin": -1,
                  "scan_delay_sleeps": 0, "scan_end_spins": -1, "scan_poison_chunk": -1,
-                 "fields_kernel": 0}
+                 "fields_kernel": 0, "onepass_poison_tile": -1}
 
 
 # --------------------------------------------------------------- profiler
 # Profiler kernel names (mgr_internal.h KernelId).
 PROFILE_KERNELS = ("bin_count", "scan", "pack", "cell_ids", "bin_ids", "cellnum_idx", "synth",
                    "exchange", "halo", "bin_fine", "count_ids", "pack_fine", "pack_narrow",
-                   "halo_pack", "onepass")
+                   "halo_pack", "onepass", "onepass_fields")
 
 
 _prof_on = False

@@ -99,7 +99,7 @@ const char* kernel_name(int k) {
                                                "bin_ids", "cellnum_idx", "synth",
                                                "exchange", "halo", "bin_fine", "count_ids",
                                                "pack_fine", "pack_narrow", "halo_pack",
-                                               "onepass"};
+                                               "onepass", "onepass_fields"};
     return (k >= 0 && k < K_NUM_KERNELS) ? names[k] : "?";
 }
 
@@ -687,6 +687,49 @@ int mgr_partition_onepass(const mgr_plan* plan, const mgr_plan* fine_plan, void*
     if (e == hipErrorNotSupported)
         return fail(MGR_EUNSUPPORTED, "one-pass partition: shape not taken (3-D, <= 64 bins, "
                     "4-byte-multiple rows of <= 128 B holding the positions, 16-byte aligned data)");
+    HIP_OK(e);
+    return MGR_OK;
+}
+
+int mgr_partition_onepass_fields(const mgr_plan* plan, const mgr_plan* fine_plan, int nfields,
+                                 void* const* srcs, const int64_t* row_bytes, int pos_field,
+                                 int64_t pos_offset, int pos_dtype, int64_t n, int periodic,
+                                 void* const* outs, uint16_t* fine_out, int64_t cap_rows,
+                                 int64_t* bin_counts, void* workspace, void* stream) {
+    if (!plan) return fail(MGR_EINVAL, "null plan");
+    if (!srcs) return fail(MGR_EINVAL, "null srcs");
+    if (!row_bytes) return fail(MGR_EINVAL, "null row_bytes");
+    if (!bin_counts) return fail(MGR_EINVAL, "null bin_counts");
+    if (nfields < 1 || nfields > MGR_MAX_FIELDS) return fail(MGR_EINVAL, "nfields %d", nfields);
+    if (pos_field < 0 || pos_field >= nfields)
+        return fail(MGR_EINVAL, "pos_field %d of %d fields", pos_field, nfields);
+    if (n < 0) return fail(MGR_EINVAL, "n %lld", (long long)n);
+    if (cap_rows < 0) return fail(MGR_EINVAL, "cap_rows %lld", (long long)cap_rows);
+    if (n > 0) {
+        if (!outs) return fail(MGR_EINVAL, "null outs");
+        if (!workspace) return fail(MGR_EINVAL, "null workspace");
+        for (int f = 0; f < nfields; ++f) {
+            if (!srcs[f]) return fail(MGR_EINVAL, "srcs[%d]: null source", f);
+            if (!outs[f] && f != pos_field)
+                return fail(MGR_EINVAL, "outs[%d]: null output (only the position field's may be)", f);
+        }
+    }
+    if (fine_plan && !fine_out) return fail(MGR_EINVAL, "fine_plan without fine_out");
+    mgr::Geom g = plan->g;
+    const char* why = mgr::onepass_fields_refusal(g, nfields, srcs, row_bytes, pos_field,
+                                                  pos_offset, pos_dtype, n, outs, fine_out);
+    if (why) return fail(MGR_EUNSUPPORTED, "one-pass fields partition: shape not taken (%s)", why);
+    pos_modes(g, pos_dtype);
+    mgr::FineGeom fg;
+    if (fine_plan) {
+        int rc = fine_geom(plan, fine_plan, g, fg);
+        if (rc) return rc;
+    }
+    const hipError_t e = mgr::launch_onepass_fields(
+        g, fine_plan ? &fg : nullptr, nfields, srcs, row_bytes, pos_field, pos_offset, pos_dtype, n,
+        periodic, outs, fine_out, cap_rows, bin_counts, workspace, (hipStream_t)stream);
+    if (e == hipErrorNotSupported)
+        return fail(MGR_EUNSUPPORTED, "one-pass fields partition: shape not taken");
     HIP_OK(e);
     return MGR_OK;
 }

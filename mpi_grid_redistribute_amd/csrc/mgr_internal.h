@@ -98,7 +98,7 @@ int nbits_for(int nbins);
 // Kernel ids for the profiler.
 enum KernelId { K_BIN_COUNT, K_SCAN, K_PACK, K_CELL_IDS, K_BIN_IDS, K_CELLNUM_IDX, K_SYNTH,
                 K_EXCHANGE, K_HALO, K_BIN_FINE, K_COUNT_IDS, K_PACK_FINE, K_PACK_NARROW,
-                K_HALO_PACK, K_ONEPASS, K_NUM_KERNELS };
+                K_HALO_PACK, K_ONEPASS, K_ONEPASS_FIELDS, K_NUM_KERNELS };
 const char* kernel_name(int k);
 void prof_begin(hipStream_t s, int k);
 void prof_end(hipStream_t s, int k);
@@ -154,6 +154,18 @@ hipError_t launch_onepass(const Geom& g, const FineGeom* fg, void* data, int64_t
                           int64_t pos_off, int pos_dtype, int64_t n, int periodic, void* out,
                           uint16_t* fine_out, int64_t cap, int64_t* bin_counts, void* workspace,
                           hipStream_t s);
+// One-pass source partition of a SoA payload (mgr_onepass_fields.hip,
+// mgr_partition_onepass_fields); onepass_fields_refusal: NULL when the kernel
+// takes the shape, else the argument that rules it out.
+const char* onepass_fields_refusal(const Geom& g, int nf, void* const* srcs,
+                                   const int64_t* row_bytes, int pos_field, int64_t pos_off,
+                                   int pos_dtype, int64_t n, void* const* outs,
+                                   const uint16_t* fine_out);
+hipError_t launch_onepass_fields(const Geom& g, const FineGeom* fg, int nf, void* const* srcs,
+                                 const int64_t* row_bytes, int pos_field, int64_t pos_off,
+                                 int pos_dtype, int64_t n, int periodic, void* const* outs,
+                                 uint16_t* fine_out, int64_t cap, int64_t* bin_counts,
+                                 void* workspace, hipStream_t s);
 hipError_t launch_halo_flags(const void* pos, int pos_dtype, int64_t n, int64_t stride, int dim,
                              const double* hi, const double* lo, uint16_t* flags, hipStream_t s);
 
@@ -185,6 +197,8 @@ struct Hooks {
     int scan_poison_chunk = -1;   // >= 0: that scan chunk publishes poisoned (a failed scan)
     int fields_kernel = 0;        // multi-field packs: 0 product choice, 1 per-wave image,
                                   // 2 tile image, 3 cooperative (where they take the fields)
+    int onepass_poison_tile = -1; // >= 0: the multi-field one-pass tile with that ticket treats
+                                  // its look-back as given up (a failed partition)
 };
 // The scan kernel's copy of the race-test hooks (kernel argument).
 struct ScanTest {

@@ -187,6 +187,18 @@ def _alias_rows(position, fields):
     return fields[0] if len(fields) == 1 else None
 
 
+def _pos_field(addrs, row_bytes, pos_addr, pos_stride_bytes, esz):
+    """(field, byte offset) when three coordinates at ``pos_addr`` lie inside the
+    first row of one of the fields at ``addrs`` and step by that field's row
+    bytes -- the positions are that field, or a strided view inside it --
+    else (-1, 0)."""
+    for f, (a, rb) in enumerate(zip(addrs, row_bytes)):
+        o = pos_addr - a
+        if 0 <= o and o + 3 * esz <= rb and pos_stride_bytes == rb:
+            return f, o
+    return -1, 0
+
+
 def _results(fields, outs, m, multi):
     """Outputs of m rows in the caller's containers: one array, or a tuple in
     the order of the fields."""
@@ -1005,6 +1017,177 @@ class GridPartitioner:
                   _lib.ptr(ws), _lib.stream_handle(stream))
         return out, fo, counts, cap
 
+    def partition_onepass_fields_device(self, flats, row_bytes, pos_tensor, periodic=True,
+                                        stream=None, fine_cells=None, cap_rows=None):
+        """partition_onepass_device of a SoA payload
+        (mgr_partition_onepass_fields): ``flats`` (uint8 device tensors of
+        n * row_bytes[f] bytes each) are read ONCE, binned by ``pos_tensor`` --
+        a device float32 / float64 (n, >= 3) tensor with unit column stride,
+        wrapped in place -- and scattered into the send_buff list of every
+        field: bin b's rows of field f, in order, from row b * cap of
+        ``outs[f]`` (their fine cells from fine_out[b * cap]).  If
+        ``pos_tensor`` lies inside one of ``flats`` with that field's row bytes
+        as its row stride (the field itself, or a strided view inside a wider
+        field), that field is the position field; otherwise the positions ride
+        as an extra staged field without an output.  Returns (outs, fine_out
+        or None, counts, cap) device tensors without a host sync; a count
+        above cap means the bin did not fit (partition_lists redoes the
+        partition), -1 counts a failed look-back (every count is then -1).
+        ``cap_rows``: rows per bin region (default 1.25 x the mean + 4096).
+        The outputs, counts and workspace are cached per (n, row bytes, cap,
+        fine, position field) and REUSED by the next call of the same shape:
+        a caller that keeps results across calls copies them.  MgrError
+        (MGR_EUNSUPPORTED) for shapes the kernel does not take -- among them
+        positions outside the fields whose n rows of stride(0) elements do not
+        fit their tensor's storage (a column-offset view of a wider tensor)."""
+        n = int(pos_tensor.shape[0])
+        nf = len(flats)
+        rbs = [int(b) for b in row_bytes]
+        esz = pos_tensor.element_size()
+        if pos_tensor.dim() != 2 or pos_tensor.shape[1] < 3 or (n and pos_tensor.stride(1) != 1):
+            raise ValueError("pos_tensor must be (n, >= 3) with unit column stride")
+        if nf < 1 or nf > MAX_FIELDS:
+            raise ValueError(f"1..{MAX_FIELDS} fields (got {nf})")
+        srcs = [t.data_ptr() for t in flats]
+        pf, off = (_pos_field(srcs, rbs, pos_tensor.data_ptr(), pos_tensor.stride(0) * esz, esz)
+                   if n else (-1, 0))
+        extra = pf < 0
+        if extra:   # the positions as one more staged field, not scattered
+            if nf + 1 > MAX_FIELDS:
+                raise ValueError(f"one-pass partition: at most {MAX_FIELDS - 1} fields when the "
+                                 f"positions are staged as an extra field (got {nf})")
+            prb = int(pos_tensor.stride(0)) * esz if n else 3 * esz
+            # the kernel stages (and, wrapping, writes back) n whole rows of
+            # stride(0) elements from the view's first element: they must lie
+            # inside the tensor's storage -- a column-offset view of a wider
+            # tensor (X[:, 4:7]) would run past X's end in its last row
+            st = pos_tensor.untyped_storage()
+            if n and pos_tensor.data_ptr() - st.data_ptr() + n * prb > st.nbytes():
+                raise _lib.MgrError(
+                    "mgr_partition_onepass_fields failed (-4): pos_tensor: a view whose last "
+                    "row of stride(0) elements ends beyond its storage cannot be staged as a field")
+            pf = nf
+            srcs.append(pos_tensor.data_ptr())
+            rbs.append(prb)
+        cap = int(cap_rows) if cap_rows is not None else (5 * n) // (4 * self.nbins) + 4096
+        key = ("onepass_fields", n, tuple(rbs), cap, fine_cells is not None, pf, extra)
+        if key not in self._cache:
+            wsb = _lib.load().mgr_onepass_workspace_bytes(n, self.nbins)
+            ws = torch.empty(max(int(wsb), 8), dtype=torch.uint8, device=self._dev)
+            outs = [torch.empty(max(self.nbins * cap * b, 1), dtype=torch.uint8, device=self._dev)
+                    for b in rbs[:nf]]
+            fo = (torch.empty(max(self.nbins * cap, 1), dtype=torch.int16, device=self._dev)
+                  if fine_cells is not None else None)
+            counts = torch.empty(self.nbins, dtype=torch.int64, device=self._dev)
+            self._cache = {key: (ws, outs, fo, counts)}
+        ws, outs, fo, counts = self._cache[key]
+        self.last_counts = counts
+        fplan = self._fine_plan(fine_cells) if fine_cells is not None else None
+        _lib.call("mgr_partition_onepass_fields", self._plan.h, fplan.h if fplan else None,
+                  len(srcs), _ptrs(srcs), _i64s(rbs), pf, int(off), pos_code(pos_tensor.dtype), n,
+                  int(bool(periodic)), _ptrs([o.data_ptr() for o in outs] + [0] * extra),
+                  _lib.ptr(fo), cap, _lib.ptr(counts), _lib.ptr(ws), _lib.stream_handle(stream))
+        return outs, fo, counts, cap
+
+    # partition_lists of a SoA payload: the one-pass kernel where it takes the
+    # shape (True), or the two-pass bin + scan + pack for every shape (False).
+    # Decided by the A/B of the two source sides on 64M config-5 rows
+    # (tools/onepass_fields_ab.py, profiles/round7/onepass_fields_ab.json,
+    # DESIGN.md §3.7): two-pass 1.51 ms, one-pass 1.64 ms -- the two-pass is
+    # the default; the one-pass runs with this set on the partitioner, and
+    # through partition_onepass_fields_device.
+    soa_onepass = False
+
+    def _two_pass_lists(self, fields, pos, periodic, fine_cells):
+        """The send_buff lists by bin + scan + mgr_pack_fields over all fields
+        (any shape): ([field][bin] flat byte slices of per-call buffers, the
+        bins' fine-cell slices or None, host counts)."""
+        n, nf, nb = fields[0].n, len(fields), self.nbins
+        rbs = [f.row_bytes for f in fields]
+        tile_rows, ws, dest = _scratch(n, nb, _tile_hint(rbs), self._dev)
+        stream = _lib.stream_handle()
+        cnt_d = torch.empty(nb, dtype=torch.int64, device=self._dev)
+        fid = fido = None
+        if fine_cells is None:
+            _lib.call("mgr_bin_count", self._plan.h, ctypes.c_void_p(pos.addr), pos.code, n,
+                      pos.stride, int(bool(periodic)), _lib.ptr(dest), tile_rows,
+                      _lib.ptr(ws), stream)
+        else:
+            fid = torch.empty(max(n, 1), dtype=torch.int16, device=self._dev)
+            fido = torch.empty(max(n, 1), dtype=torch.int16, device=self._dev)
+            _lib.call("mgr_bin_count_fine", self._plan.h, self._fine_plan(fine_cells).h,
+                      ctypes.c_void_p(pos.addr), pos.code, n, pos.stride, int(bool(periodic)),
+                      _lib.ptr(dest), _lib.ptr(fid), tile_rows, _lib.ptr(ws), stream)
+        pos.finish()
+        _lib.call("mgr_scan", n, nb, tile_rows, _lib.ptr(ws), _lib.ptr(cnt_d), stream)
+        outs = [torch.empty(max(n * rb, 1), dtype=torch.uint8, device=self._dev) for rb in rbs]
+        _lib.call("mgr_pack_fields", nf, _ptrs([f.flat.data_ptr() for f in fields]),
+                  _i64s(rbs), n, _lib.ptr(dest), nb, -1, tile_rows, _lib.ptr(ws),
+                  _ptrs([o.data_ptr() for o in outs]), -1, None, _lib.ptr(fid),
+                  _lib.ptr(fido), None, 0, -1, stream)
+        counts = cnt_d.cpu().numpy()
+        check_counts(counts, [])
+        st = np.concatenate([[0], np.cumsum(counts)])
+        parts = [[outs[i][int(st[b]) * rbs[i]:int(st[b + 1]) * rbs[i]] for b in range(nb)]
+                 for i in range(nf)]
+        fparts = ([fido[int(st[b]):int(st[b + 1])] for b in range(nb)]
+                  if fine_cells is not None else None)
+        return parts, fparts, counts
+
+    # "onepass" / "twopass": how the last SoA partition_lists call made its lists
+    last_lists_path = None
+
+    def _partition_lists_fields(self, data, position, periodic, fine_cells):
+        """partition_lists of a tuple / list payload: per field the list of
+        per-bin arrays (freshly allocated, never views of a cached buffer)."""
+        fields, _ = _payload(data, self._dev)
+        pos = Positions(position, self.dim, self._dev, data_rows=_alias_rows(position, fields))
+        n, nf, nb = fields[0].n, len(fields), self.nbins
+        if pos.n != n:
+            raise ValueError("data and position row counts differ")
+        rbs = [f.row_bytes for f in fields]
+        esz = _lib.POS_ITEMSIZE[pos.code]
+        cuda_out = fields[0].kind == "torch" and fields[0].out_device.type == "cuda"
+        counts = None
+        if (self.soa_onepass and n and self.dim == 3
+                and pos.code in (_lib.MGR_F32, _lib.MGR_F64)):
+            if pos.t is not None:
+                pos_t = pos.t
+            else:   # a numpy view of a field: the same view of the field's device bytes
+                base = pos._alias_rows.flat.view(_TORCH_POS[pos.code])
+                pos_t = torch.as_strided(
+                    base, (n, 3), (pos.stride, 1),
+                    (pos.addr - base.untyped_storage().data_ptr()) // esz)
+            try:
+                outs, fo, cnt_d, cap = self.partition_onepass_fields_device(
+                    [f.flat for f in fields], rbs, pos_t, periodic, fine_cells=fine_cells)
+                counts = cnt_d.cpu().numpy()
+                pos.finish()
+                check_counts(counts, [])
+                if (counts > cap).any():
+                    counts = None          # a bin outgrew its region: the two-pass path
+                    periodic = False       # the positions are wrapped already (S2)
+                else:
+                    fresh = (lambda t: t.clone()) if cuda_out else (lambda t: t)
+                    parts = [[fresh(outs[i][b * cap * rbs[i]:(b * cap + int(counts[b])) * rbs[i]])
+                              for b in range(nb)] for i in range(nf)]
+                    fparts = ([fresh(fo[b * cap:b * cap + int(counts[b])]) for b in range(nb)]
+                              if fo is not None else None)
+            except _lib.MgrError as e:
+                if "(-4)" not in str(e):      # MGR_EUNSUPPORTED: the two-pass path
+                    raise
+        self.last_lists_path = "onepass"
+        if counts is None:
+            self.last_lists_path = "twopass"
+            parts, fparts, counts = self._two_pass_lists(fields, pos, periodic, fine_cells)
+        res = tuple([f.wrap(p, int(c)) for p, c in zip(parts[i], counts)]
+                    for i, f in enumerate(fields))
+        if fine_cells is None:
+            return res
+        if cuda_out:
+            return res, fparts            # int16 tensors holding the uint16 cells
+        return res, [f.cpu().numpy().view(np.uint16) for f in fparts]
+
     def partition_lists(self, data, position, periodic=True, fine_cells=None):
         """The reference's send_buff list (redist.py:195-198: send_buff[i] =
         data[rank_to_send == i], original order kept): one array per bin, in
@@ -1015,7 +1198,18 @@ class GridPartitioner:
         (partition_onepass_device: every record read once); any other shape,
         or a bin that outgrows its region, through the classic bin + scan +
         pack (a redo re-bins the stored, already wrapped positions with
-        periodic = 0 -- identical bins, S2 -- so nothing is wrapped twice)."""
+        periodic = 0 -- identical bins, S2 -- so nothing is wrapped twice).
+        ``data`` may be a tuple / list of arrays sharing axis 0 (SoA, at most
+        MAX_FIELDS; with ``soa_onepass`` set one fewer when ``position`` is
+        not one of them, as the one-pass kernel then stages it as a field): the
+        result is then a tuple, in field order, of per-bin lists (with
+        ``fine_cells``: (that tuple, fine list)), every array freshly
+        allocated; the fields go through the multi-field one-pass kernel
+        (partition_onepass_fields_device) where it takes the shape, else --
+        or when a bin outgrows its region -- through bin + scan +
+        mgr_pack_fields over all fields."""
+        if isinstance(data, (tuple, list)):
+            return self._partition_lists_fields(data, position, periodic, fine_cells)
         rows = Rows(data, self._dev)
         pos = Positions(position, self.dim, self._dev, data_rows=rows)
         n, rb = rows.n, rows.row_bytes
@@ -1051,33 +1245,8 @@ class GridPartitioner:
                 if "(-4)" not in str(e):      # MGR_EUNSUPPORTED: the classic path
                     raise
         if counts is None:
-            tile_rows, ws, dest = _scratch(n, self.nbins, rb, self._dev)
-            stream = _lib.stream_handle()
-            cnt_d = torch.empty(self.nbins, dtype=torch.int64, device=self._dev)
-            fid = fido = None
-            if fine_cells is None:
-                _lib.call("mgr_bin_count", self._plan.h, ctypes.c_void_p(pos.addr), pos.code, n,
-                          pos.stride, int(bool(periodic)), _lib.ptr(dest), tile_rows,
-                          _lib.ptr(ws), stream)
-            else:
-                fid = torch.empty(max(n, 1), dtype=torch.int16, device=self._dev)
-                fido = torch.empty(max(n, 1), dtype=torch.int16, device=self._dev)
-                _lib.call("mgr_bin_count_fine", self._plan.h, self._fine_plan(fine_cells).h,
-                          ctypes.c_void_p(pos.addr), pos.code, n, pos.stride, int(bool(periodic)),
-                          _lib.ptr(dest), _lib.ptr(fid), tile_rows, _lib.ptr(ws), stream)
-            pos.finish()
-            _lib.call("mgr_scan", n, self.nbins, tile_rows, _lib.ptr(ws), _lib.ptr(cnt_d), stream)
-            out = torch.empty(max(n * rb, 1), dtype=torch.uint8, device=self._dev)
-            _lib.call("mgr_pack_fields", 1, _ptrs([rows.flat.data_ptr()]), _i64s([rb]), n,
-                      _lib.ptr(dest), self.nbins, -1, tile_rows, _lib.ptr(ws),
-                      _ptrs([out.data_ptr()]), -1, None, _lib.ptr(fid), _lib.ptr(fido), None,
-                      0, -1, stream)
-            counts = cnt_d.cpu().numpy()
-            check_counts(counts, [])
-            st = np.concatenate([[0], np.cumsum(counts)])
-            parts = [out[int(st[b]) * rb:int(st[b + 1]) * rb] for b in range(self.nbins)]
-            fparts = ([fido[int(st[b]):int(st[b + 1])] for b in range(self.nbins)]
-                      if fine_cells is not None else None)
+            parts, fparts, counts = self._two_pass_lists([rows], pos, periodic, fine_cells)
+            parts = parts[0]
         res = [rows.wrap(p, int(c)) for p, c in zip(parts, counts)]
         if fine_cells is None:
             return res
