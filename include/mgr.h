@@ -34,6 +34,9 @@ extern "C" {
 #define MGR_MAX_DIM 8
 #define MGR_MAX_BINS 4096
 #define MGR_MAX_FIELDS 16
+/* Fields of one multi-selection pack (mgr_msel_pack_fields / _placed): a SoA
+ * payload of MGR_MAX_FIELDS fields, the positions and the face flags.      */
+#define MGR_MSEL_MAX_FIELDS (MGR_MAX_FIELDS + 2)
 #define MGR_UNIQUE_ID_BYTES 128
 
 typedef enum {
@@ -383,10 +386,15 @@ int mgr_msel_count(const uint16_t* flags, int64_t n, int nsets, const int* masks
 int mgr_msel_pack(const void* src, int64_t row_bytes, int64_t n, const uint16_t* flags,
                   int nsets, const int* masks, int tile_rows, const void* workspace,
                   void* const* dsts, void* stream);
-/* mgr_msel_pack of nfields (1..3) fields of the same rows in one pass (the
- * flags read and the sets listed once): srcs[f] rows of row_bytes[f]; set k
- * of field f goes to dsts[f * nsets + k]; field 0's NULLs decide which sets
- * are written.                                                            */
+/* mgr_msel_pack of nfields (1..MGR_MSEL_MAX_FIELDS) fields of the same rows
+ * in one pass (the flags read and the sets listed once): srcs[f] rows of
+ * row_bytes[f]; set k of field f goes to dsts[f * nsets + k]; field 0's NULLs
+ * decide which sets are written.  Up to 3 fields run the three-field kernel,
+ * 4 and more the wide one, whose destination table holds 384 pointers per
+ * launch: when nfields * nsets exceeds that, the fields are packed in groups
+ * of 384 / nsets per launch (the flags and lists once per group; 17 fields of
+ * the 26-set one-rank halo: two launches).  The placed form passes one pointer
+ * per field and is never split.                                            */
 int mgr_msel_pack_fields(int nfields, const void* const* srcs, const int64_t* row_bytes, int64_t n,
                          const uint16_t* flags, int nsets, const int* masks, int tile_rows,
                          const void* workspace, void* const* dsts, void* stream);

@@ -35,7 +35,9 @@ extern "C" {
  * cooperative kernel -- each where it takes the fields, else the next),
  * "onepass_poison_tile" (mgr_partition_onepass_fields: the tile with this
  * ticket treats its look-back as given up -- it publishes its prefix
- * poisoned and writes no rows: a deterministic failed partition, -1 = none).
+ * poisoned and writes no rows: a deterministic failed partition, -1 = none),
+ * "msel_wide" (1: mgr_msel_pack* run the wide multi-selection kernel also
+ * for 1..3 fields, which otherwise take the three-field kernel).
  * Each call publishes a new immutable
  * snapshot of every hook (the library's launches read one snapshot each);
  * < 0 for an unknown key or an out-of-range value.                         */

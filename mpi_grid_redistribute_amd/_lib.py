@@ -24,6 +24,8 @@ MGR_F16, MGR_I8, MGR_I16, MGR_U8, MGR_U16, MGR_U32, MGR_U64, MGR_B8 = 5, 6, 7, 8
 POS_ITEMSIZE = {MGR_F16: 2, MGR_F32: 4, MGR_F64: 8, MGR_I8: 1, MGR_I16: 2, MGR_I32: 4,
                 MGR_I64: 8, MGR_U8: 1, MGR_U16: 2, MGR_U32: 4, MGR_U64: 8, MGR_B8: 1}
 UNIQUE_ID_BYTES = 128
+MAX_FIELDS = 16                      # mgr.h MGR_MAX_FIELDS: fields of a SoA payload
+MSEL_MAX_FIELDS = MAX_FIELDS + 2     # mgr.h MGR_MSEL_MAX_FIELDS: + positions + face flags
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -195,7 +197,7 @@ HOOK_DEFAULTS = {"tile_rounds": 0, "scan_chunk": 2048, "scan_max_chunks": 1024,
                  "scan_spins": 1 << 24, "pack_img_all": 0, "rank_rows": 0, "bin_unstaged": 0,
                  "bin_generic": 0, "pack_generic": 0, "scan_delay_bin": -1,
                  "scan_delay_sleeps": 0, "scan_end_spins": -1, "scan_poison_chunk": -1,
-                 "fields_kernel": 0, "onepass_poison_tile": -1}
+                 "fields_kernel": 0, "onepass_poison_tile": -1, "msel_wide": 0}
 
 
 # --------------------------------------------------------------- profiler

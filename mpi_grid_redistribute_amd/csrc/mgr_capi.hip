@@ -461,8 +461,8 @@ int mgr_msel_pack_fields(int nfields, const void* const* srcs, const int64_t* ro
                          const void* workspace, void* const* dsts, void* stream) {
     int rc = check_tile(tile_rows);
     if (rc || (rc = check_sets(nsets, masks))) return rc;
-    if (nfields < 1 || nfields > 3 || !srcs || !row_bytes)
-        return fail(MGR_EINVAL, "nfields %d (1..3)", nfields);
+    if (nfields < 1 || nfields > MGR_MSEL_MAX_FIELDS || !srcs || !row_bytes)
+        return fail(MGR_EINVAL, "nfields %d (1..%d)", nfields, MGR_MSEL_MAX_FIELDS);
     for (int f = 0; f < nfields; ++f)
         if (row_bytes[f] < 1) return fail(MGR_EINVAL, "row_bytes %lld", (long long)row_bytes[f]);
     if (n > 0 && (!flags || !workspace || !dsts)) return fail(MGR_EINVAL, "null argument");
@@ -480,8 +480,8 @@ int mgr_msel_pack_placed(int nfields, const void* const* srcs, const int64_t* ro
                          const void* workspace, void* const* dsts, int64_t cap_rows, void* stream) {
     int rc = check_tile(tile_rows);
     if (rc || (rc = check_sets(nsets, masks))) return rc;
-    if (nfields < 1 || nfields > 3 || !srcs || !row_bytes)
-        return fail(MGR_EINVAL, "nfields %d (1..3)", nfields);
+    if (nfields < 1 || nfields > MGR_MSEL_MAX_FIELDS || !srcs || !row_bytes)
+        return fail(MGR_EINVAL, "nfields %d (1..%d)", nfields, MGR_MSEL_MAX_FIELDS);
     if (cap_rows < 0) return fail(MGR_EINVAL, "cap_rows %lld", (long long)cap_rows);
     for (int f = 0; f < nfields; ++f)
         if (row_bytes[f] < 1) return fail(MGR_EINVAL, "row_bytes %lld", (long long)row_bytes[f]);

@@ -199,6 +199,7 @@ struct Hooks {
                                   // 2 tile image, 3 cooperative (where they take the fields)
     int onepass_poison_tile = -1; // >= 0: the multi-field one-pass tile with that ticket treats
                                   // its look-back as given up (a failed partition)
+    int msel_wide = 0;            // 1: the wide multi-selection pack also for 1..3 fields
 };
 // The scan kernel's copy of the race-test hooks (kernel argument).
 struct ScanTest {

@@ -47,6 +47,12 @@ redistribute_by_position hands over the spare rows of its output, so the
 final concatenate(data, overload) (:166) costs nothing while the halo fits;
 when the positions are not returned they are not carried at all (the flags
 already hold everything the selections read).
+
+A SoA payload (a list of fields, at most _lib.MAX_FIELDS) moves the same way:
+the fields of a pack, a staging buffer or a message group are then the
+payload's fields, the positions when carried, and the flags -- up to
+_lib.MSEL_MAX_FIELDS = MAX_FIELDS + 2, which mgr_msel_pack_fields takes in one
+call (the wide kernel from 4 fields on, mgr.h).
 """
 from __future__ import annotations
 
@@ -114,22 +120,37 @@ def self_halo_pieces(dim):
     return buf
 
 
-def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, pending=()):
+def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, pending=(),
+               multi=False):
     """exchange_overload when every neighbour is this rank: all pieces are
     known from the local rows' flags, so one selection pass counts them all
     and one multi-set pack writes every row straight to each of its pieces
     in the store -- the local rows are read once, not once per dimension,
-    and nothing is staged or received."""
+    and nothing is staged or received.  ``srcs`` / ``rbs``: the payload's
+    fields, then the positions when carried; ``multi``: the payload is a list
+    of fields (arena[0] a list of stores, the data returned as a list)."""
     pieces = self_halo_pieces(dim)
     h, cnt = sel.msel_masks(flags, n, pieces, "_self")
     F = len(rbs)
+    D = F - 1 if carry_pos else F                         # payload fields
+
+    def stores():
+        return (list(arena[0]) if multi else [arena[0]]) + ([arena[1]] if carry_pos else [])
+
+    def result(out, total, in_arena):
+        data = out[:D] if multi else out[0]
+        return data, (out[D] if carry_pos else None), total, in_arena
+
+    def nothing(in_arena):
+        empty = torch.empty(0, dtype=torch.uint8, device=dev)
+        return result([empty] * F, 0, in_arena)
     placed = arena is not None and arena[3] > 0
     # the one host read is enqueued BEFORE the placed pack and waited for on
     # its own event: the host finishes this call (and launches the caller's
     # next work) while the pack runs, instead of idling the GPU after it
     read = sel.to_host_start([cnt] + list(pending))
     if placed:   # into the arena before the sizes are known: no gap at the sync
-        ast = [arena[0]] + ([arena[1]] if carry_pos else [])
+        ast = stores()
         sel.msel_pack_placed(h, srcs, rbs, [ast[f][arena[2] * rbs[f]:] for f in range(F)],
                              arena[3])
     got = sel.to_host_wait(read)                          # the one host sync
@@ -141,13 +162,11 @@ def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, 
     if placed and total <= arena[3]:
         _lib.alg_add("halo_pack", 2 * n + 2 * total * sum(rbs))
         if not total:
-            empty = torch.empty(0, dtype=torch.uint8, device=dev)
-            return empty, (empty if carry_pos else None), 0, True
+            return nothing(True)
         b = arena[2]
-        out = [ast[f][b * rbs[f]:(b + total) * rbs[f]] for f in range(F)]
-        return out[0], (out[1] if carry_pos else None), total, True
+        return result([ast[f][b * rbs[f]:(b + total) * rbs[f]] for f in range(F)], total, True)
     if arena is not None and total <= arena[3]:
-        st, base, in_arena = [arena[0]] + ([arena[1]] if carry_pos else []), arena[2], True
+        st, base, in_arena = stores(), arena[2], True
     else:
         st = [torch.empty(max(total, 1) * rb, dtype=torch.uint8, device=dev) for rb in rbs]
         base, in_arena = 0, False
@@ -157,10 +176,9 @@ def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, 
     if total:
         sel.msel_pack_fields(h, srcs, rbs, dsts, total)
     if not total:
-        empty = torch.empty(0, dtype=torch.uint8, device=dev)
-        return empty, (empty if carry_pos else None), 0, in_arena
-    out = [st[f][base * rbs[f]:(base + total) * rbs[f]] for f in range(F)]
-    return out[0], (out[1] if carry_pos else None), total, in_arena
+        return nothing(in_arena)
+    return result([st[f][base * rbs[f]:(base + total) * rbs[f]] for f in range(F)], total,
+                  in_arena)
 
 
 def neighbours(R, d, periodic):
@@ -257,8 +275,9 @@ class DeviceSelect:
                   tile_rows, _lib.ptr(ws), ptrs, _lib.stream_handle())
 
     def msel_pack_fields(self, handle, srcs, row_bytes, dsts, rows_out=0):
-        """Several fields of the same rows in one pass: dsts[f][k] as in
-        msel_pack (field 0's None entries decide which sets are written).
+        """Several fields (at most _lib.MSEL_MAX_FIELDS) of the same rows in
+        one pass: dsts[f][k] as in msel_pack (field 0's None entries decide
+        which sets are written).
         ``rows_out``: the rows the written sets hold (byte accounting)."""
         n, flags, cb, k, ws, tile_rows = handle
         _lib.alg_add("halo_pack", 2 * n + 2 * rows_out * sum(row_bytes))
@@ -311,11 +330,23 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     own with headroom.  Returns (overload data flat, overload positions flat
     or None, rows, whether they stayed in the arena).  ``pending``: device
     count tensors of the caller whose check (check_counts) rides on this
-    exchange's first host read."""
+    exchange's first host read.
+
+    SoA payloads: ``data_flat`` and ``rbd`` may be lists, one entry per
+    payload field (at most MAX_FIELDS); every field moves with the same
+    selections -- one count and one pack launch per step for all of them,
+    one message group per dimension.  ``arena[0]`` is then a list of stores
+    and the returned overload data a list in the same order."""
     dim = R.dim
     assert len(overload_lengths) == dim, \
         "Overload lengths must be the same length as the dimensions"  # redist.py:245
-    dev = data_flat.device
+    multi = isinstance(data_flat, (list, tuple))
+    datas, rbds = (list(data_flat), list(rbd)) if multi else ([data_flat], [rbd])
+    D = len(datas)                                        # payload fields
+    if not 1 <= D == len(rbds) <= _lib.MAX_FIELDS:
+        raise ValueError(f"1..{_lib.MAX_FIELDS} payload fields with their row bytes "
+                         f"(got {D} and {len(rbds)})")
+    dev = datas[0].device
     sel = sel or DeviceSelect(dev)
     carry_pos = pos_flat is not None
     if flags is None:
@@ -323,15 +354,19 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
         flags = sel.flags(pos_flat, n, ncols, pos_code, dim, hi, lo)
     flags_flat = flags.reshape(-1).view(torch.uint8)[: 2 * n]
     isz = _lib.POS_ITEMSIZE[pos_code]
-    srcs = [data_flat] + ([pos_flat] if carry_pos else []) + [flags_flat]
-    rbs = [rbd] + ([ncols * isz] if carry_pos else []) + [2]
+    srcs = datas + ([pos_flat] if carry_pos else []) + [flags_flat]
+    rbs = rbds + ([ncols * isz] if carry_pos else []) + [2]
     F, FL = len(rbs), len(rbs) - 1                        # fields; the flags field
+
+    def result(out, rows, in_arena):
+        """out: the fields' overload rows (payload, then positions)."""
+        return (out[:D] if multi else out[0]), (out[D] if carry_pos else None), rows, in_arena
     me = transport.rank
     nb = [neighbours(R, d, periodic) for d in range(dim)]
     selfd = [a == me and b == me for a, b, _, _ in nb]
     if dim <= 3 and all(selfd) and all(ka and kb for _, _, ka, kb in nb):
         return _self_halo(transport, sel, srcs[:F - 1], rbs[:F - 1], flags, n, dim, carry_pos,
-                          arena, dev, pending)
+                          arena, dev, pending, multi)
     for c in pending:   # (the general path reads them here)
         check_counts(c.cpu().numpy(), [])
 
@@ -366,9 +401,9 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     st = [None] * F
     base, cap, in_arena = 0, 0, False
     if arena is not None:
-        st[0] = arena[0]
+        st[:D] = list(arena[0]) if multi else [arena[0]]
         if carry_pos:
-            st[1] = arena[1]
+            st[D] = arena[1]
         base, cap, in_arena = arena[2], arena[3], True
         st[FL] = torch.empty(max(cap, 1) * 2, dtype=torch.uint8, device=dev)
     fbase = [base] * (F - 1) + [0]                           # the flags store is our own
@@ -510,6 +545,5 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     if transport.any_failed(failed):
         check_counts([-1], [])
     if not m:
-        empty = torch.empty(0, dtype=torch.uint8, device=dev)
-        return empty, (empty if carry_pos else None), 0, in_arena
-    return store(0, 0, m), (store(1, 0, m) if carry_pos else None), m, in_arena
+        return result([torch.empty(0, dtype=torch.uint8, device=dev)] * (F - 1), 0, in_arena)
+    return result([store(f, 0, m) for f in range(F - 1)], m, in_arena)

@@ -206,7 +206,7 @@ def _results(fields, outs, m, multi):
     return res if multi else res[0]
 
 
-MAX_FIELDS = 16   # mgr.h MGR_MAX_FIELDS
+MAX_FIELDS = _lib.MAX_FIELDS   # mgr.h MGR_MAX_FIELDS
 
 
 # The row size the tile policy sizes multi-field packs for: the cooperative
@@ -506,8 +506,11 @@ class MPIGridRedistributor:
         halo = overload_lengths is not None
         if halo:
             if multi:
-                raise NotImplementedError("overload_lengths with a SoA (tuple) payload: pass "
-                                          "one array (e.g. a structured record)")
+                raise NotImplementedError(
+                    "overload_lengths with a SoA (tuple) payload in one call: use "
+                    "redistribute_by_position(fields, pos, return_positions=True), then "
+                    "exchange_overload_by_position(fields, local_pos, overload_lengths) on "
+                    "the result, and concatenate the two per field")
             self._check_halo(overload_lengths)
             return self._redistribute_halo(data, position, fields[0], pos, periodic,
                                            overload_lengths, return_positions)
@@ -643,10 +646,17 @@ class MPIGridRedistributor:
         """redist.py:202-309: the overload (halo) rows of this rank's cell
         from its neighbours; ``data``/``position`` are this rank's local rows
         (already redistributed).  ``return_positions`` (ignored by the
-        reference) returns (data, positions)."""
+        reference) returns (data, positions).  ``data`` may be a SoA payload,
+        a tuple / list of arrays sharing axis 0 as in
+        ``redistribute_by_position``: every field's overload rows move with
+        the same selections (one flags pass, one selection count and one pack
+        launch per step, one message group per dimension) and come back as a
+        tuple in the same order -- what the reference gives called once per
+        field with the same positions."""
         self._check_halo(overload_lengths)
+        fields, multi = _payload(data, self._dev)
         self.comm.reset_traffic()
-        rows = Rows(data, self._dev)
+        rows = fields[0]
         prow = Rows(position, self._dev)
         if not (isinstance(position, (np.ndarray, torch.Tensor)) and position.ndim == 2
                 and position.shape[1] >= self.dim):
@@ -661,11 +671,11 @@ class MPIGridRedistributor:
             hi, lo = thresholds(self, overload_lengths)
             flags = sel.flags(prow.flat, rows.n, ncols, code, self.dim, hi, lo)
             pflat = None
-        ov_d, ov_p, mo, _ = exchange_overload(self, self.comm, rows.flat, rows.row_bytes,
-                                              pflat, ncols, code, rows.n,
-                                              list(overload_lengths), periodic=bool(periodic),
-                                              sel=sel, flags=flags)
-        res = rows.wrap(ov_d, mo)
+        ov_d, ov_p, mo, _ = exchange_overload(
+            self, self.comm, [f.flat for f in fields] if multi else rows.flat,
+            [f.row_bytes for f in fields] if multi else rows.row_bytes, pflat, ncols, code,
+            rows.n, list(overload_lengths), periodic=bool(periodic), sel=sel, flags=flags)
+        res = _results(fields, ov_d if multi else [ov_d], mo, multi)
         return (res, prow.wrap(ov_p, mo)) if return_positions else res
 
     def fine_cell_sort(self, data, position, fine_cells, return_positions=False, fine_ids=None):
