@@ -241,6 +241,42 @@ int mgr_pack_fields(int nfields, const void* const* srcs, const int64_t* row_byt
                     void* const* redirect_dsts, const uint16_t* ids_src, uint16_t* ids_dst,
                     uint16_t* ids_redirect_dst, int64_t tile_begin, int64_t tile_end,
                     void* stream);
+/* -------------------------------------------------------------- unpack --
+ * The return path: the inverse of mgr_pack (redist.py:195-199 is the
+ * permutation being inverted -- send_buff[i] = data[rank_to_send == i], then
+ * the alltoall).  For the same (dest, nbins, drop_bin, tile_rows, workspace,
+ * redirect_bin) that a mgr_pack call takes, let slot(r) be the row index at
+ * which that pack writes source row r: an index into dst, or into
+ * redirect_dst when row r's bin is redirect_bin.  mgr_unpack writes
+ *     out[r] = packed[slot(r)]
+ * for every row r whose bin is not the drop bin; a row of redirect_bin reads
+ * redirect_src[slot(r)] instead, and a row of the drop bin gets row_bytes
+ * zero bytes, so out (n rows) is fully defined.  The rows of packed are any
+ * row_bytes, unrelated to what the pack moved: per-row results computed where
+ * the packed rows went, brought back onto their source rows.
+ * dest and workspace must be as the count producer and mgr_scan left them;
+ * they are only read: no binning, no scan, no allocation, no host sync,
+ * stream-ordered.  After a failed scan nothing is written (as the packs).
+ * out must not alias packed or redirect_src.  MGR_EINVAL: for n > 0 a null
+ * dest, workspace, out or packed; row_bytes < 1; tile_rows not a multiple of
+ * 64 in range; redirect_bin >= 0 with a null redirect_src or equal to
+ * drop_bin; redirect_bin >= nbins.  n == 0: MGR_OK, nothing is read.       */
+int mgr_unpack(const void* packed, int64_t row_bytes, int64_t n, const void* dest, int nbins,
+               int drop_bin, int tile_rows, const void* workspace, void* out, int redirect_bin,
+               const void* redirect_src, void* stream);
+/* mgr_unpack of nfields (1..MGR_MAX_FIELDS) arrays of the same rows with ONE
+ * dest: field f reads packed[f] (redirect_srcs[f]) in rows of row_bytes[f]
+ * and writes outs[f].  Up to four fields of 4-byte-multiple rows <= 64 B,
+ * <= 64 bins, move from one ranking in one launch where their signature is
+ * one the multi-field pack is built for; any other set goes field by field.
+ * tile_end < 0: every tile; else only the rows of the tiles [tile_begin,
+ * tile_end) are written (0 <= begin <= end <= the tile count, as
+ * mgr_pack_tiles).                                                         */
+int mgr_unpack_fields(int nfields, const void* const* packed, const int64_t* row_bytes, int64_t n,
+                      const void* dest, int nbins, int drop_bin, int tile_rows,
+                      const void* workspace, void* const* outs, int redirect_bin,
+                      const void* const* redirect_srcs, int64_t tile_begin, int64_t tile_end,
+                      void* stream);
 /* After mgr_scan: out[i * nbins + b] (device int64) = the first row of bin b
  * at tile tiles[i] in the packed layout (tiles[i] = the tile count: the bin's
  * end), i.e. where a chunk of tiles starts inside every bin's segment.

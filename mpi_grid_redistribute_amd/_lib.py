@@ -59,6 +59,8 @@ SIGNATURES = {
                             _P]),
     "mgr_pack_fields": (_I, [_I, _P, _P, _I64, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I64,
                              _I64, _P]),
+    "mgr_unpack": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "mgr_unpack_fields": (_I, [_I, _P, _P, _I64, _P, _I, _I, _I, _P, _P, _I, _P, _I64, _I64, _P]),
     "mgr_tile_offsets": (_I, [_P, _I64, _I, _I, _P, _I, _P, _P]),
     "mgr_partition_by_position": (_I, [_P, _P, _I, _I64, _I64, _I, _P, _I64, _P, _P, _P, _I,
                                        _P, _P]),
@@ -197,14 +199,15 @@ HOOK_DEFAULTS = {"tile_rounds": 0, "scan_chunk": 2048, "scan_max_chunks": 1024,
                  "scan_spins": 1 << 24, "pack_img_all": 0, "rank_rows": 0, "bin_unstaged": 0,
                  "bin_generic": 0, "pack_generic": 0, "scan_delay_bin": -1,
                  "scan_delay_sleeps": 0, "scan_end_spins": -1, "scan_poison_chunk": -1,
-                 "fields_kernel": 0, "onepass_poison_tile": -1, "msel_wide": 0}
+                 "fields_kernel": 0, "onepass_poison_tile": -1, "msel_wide": 0,
+                 "unpack_kernel": 0}
 
 
 # --------------------------------------------------------------- profiler
 # Profiler kernel names (mgr_internal.h KernelId).
 PROFILE_KERNELS = ("bin_count", "scan", "pack", "cell_ids", "bin_ids", "cellnum_idx", "synth",
                    "exchange", "halo", "bin_fine", "count_ids", "pack_fine", "pack_narrow",
-                   "halo_pack", "onepass", "onepass_fields")
+                   "halo_pack", "onepass", "onepass_fields", "unpack")
 
 
 _prof_on = False

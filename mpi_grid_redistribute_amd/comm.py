@@ -415,15 +415,27 @@ class TorchDistComm(Transport):
 
     def exchange_rows(self, sends, outs, row_bytes, send_counts, send_offsets, recv_counts,
                       recv_offsets):
+        # segments laid end to end from row 0 (the forward exchange: the packed
+        # send buffer is bin-major) move by split sizes alone; a layout with
+        # gaps (the return path of a redirected self segment) is gathered first
+        dense_in = np.array_equal(send_offsets, excl_cumsum(np.asarray(send_counts)))
+        dense_out = np.array_equal(recv_offsets, excl_cumsum(np.asarray(recv_counts)))
         for f, (snd, out) in enumerate(zip(sends, outs)):
             rb = row_bytes[f]
             in_split = [int(c) * rb for c in send_counts]
             out_split = [int(c) * rb for c in recv_counts]
-            # the packed send buffer is bin-major from row 0, so split sizes are enough
-            nsend = int(sum(in_split))
-            self.dist.all_to_all_single(out[: int(sum(out_split))], snd[:nsend].contiguous(),
-                                        output_split_sizes=out_split, input_split_sizes=in_split,
-                                        group=self.group)
+            nsend, nrecv = int(sum(in_split)), int(sum(out_split))
+            src = snd[:nsend].contiguous() if dense_in else torch.cat(
+                [snd[int(o) * rb:int(o) * rb + k] for o, k in zip(send_offsets, in_split)])
+            dst = out[:nrecv] if dense_out else torch.empty(nrecv, dtype=out.dtype,
+                                                            device=out.device)
+            self.dist.all_to_all_single(dst, src, output_split_sizes=out_split,
+                                        input_split_sizes=in_split, group=self.group)
+            if not dense_out:
+                at = 0
+                for o, k in zip(recv_offsets, out_split):
+                    out[int(o) * rb:int(o) * rb + k].copy_(dst[at:at + k])
+                    at += k
 
     def p2p(self, ops):
         _self_pairs(ops, self.rank)

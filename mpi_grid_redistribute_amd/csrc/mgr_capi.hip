@@ -99,7 +99,7 @@ const char* kernel_name(int k) {
                                                "bin_ids", "cellnum_idx", "synth",
                                                "exchange", "halo", "bin_fine", "count_ids",
                                                "pack_fine", "pack_narrow", "halo_pack",
-                                               "onepass", "onepass_fields"};
+                                               "onepass", "onepass_fields", "unpack"};
     return (k >= 0 && k < K_NUM_KERNELS) ? names[k] : "?";
 }
 
@@ -769,6 +769,56 @@ int mgr_pack_fields(int nfields, const void* const* srcs, const int64_t* row_byt
                                    ws, dsts, redirect_bin, redirect_bin >= 0 ? redirect_dsts : nullptr,
                                    (hipStream_t)stream, ids_src, ids_dst, ids_redirect_dst));
     return MGR_OK;
+}
+
+int mgr_unpack_fields(int nfields, const void* const* packed, const int64_t* row_bytes, int64_t n,
+                      const void* dest, int nbins, int drop_bin, int tile_rows,
+                      const void* workspace, void* const* outs, int redirect_bin,
+                      const void* const* redirect_srcs, int64_t tile_begin, int64_t tile_end,
+                      void* stream) {
+    int rc = check_tile(tile_rows);
+    if (rc) return rc;
+    if (nfields < 1 || nfields > MGR_MAX_FIELDS) return fail(MGR_EINVAL, "nfields %d", nfields);
+    if (!packed || !row_bytes || !outs) return fail(MGR_EINVAL, "null field arrays");
+    if (nbins < 1 || nbins > MGR_MAX_BINS) return fail(MGR_EINVAL, "nbins %d", nbins);
+    if (n < 0) return fail(MGR_EINVAL, "n < 0");
+    if (redirect_bin >= nbins) return fail(MGR_EINVAL, "redirect_bin out of range");
+    if (redirect_bin >= 0 && redirect_bin == drop_bin)
+        return fail(MGR_EINVAL, "redirect_bin %d is the drop bin", redirect_bin);
+    if (redirect_bin >= 0 && !redirect_srcs) return fail(MGR_EINVAL, "redirect without a source");
+    for (int f = 0; f < nfields; ++f) {
+        if (row_bytes[f] < 1) return fail(MGR_EINVAL, "field %d: row_bytes %lld", f, (long long)row_bytes[f]);
+        if (n > 0 && (!packed[f] || !outs[f])) return fail(MGR_EINVAL, "field %d: null packed/out", f);
+        if (redirect_bin >= 0 && !redirect_srcs[f])
+            return fail(MGR_EINVAL, "field %d: redirect without a source", f);
+    }
+    if (n > 0 && (!dest || !workspace)) return fail(MGR_EINVAL, "null dest/workspace");
+    if (n == 0) {
+        if (tile_end > 0 || (tile_end >= 0 && tile_begin != 0))
+            return fail(MGR_EINVAL, "tiles [%lld, %lld) of 0", (long long)tile_begin, (long long)tile_end);
+        return MGR_OK;
+    }
+    mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
+    if (tile_end >= 0) {
+        if (tile_begin < 0 || tile_end < tile_begin || tile_end > ws.T)
+            return fail(MGR_EINVAL, "tiles [%lld, %lld) of %lld", (long long)tile_begin,
+                        (long long)tile_end, (long long)ws.T);
+        if (tile_end == tile_begin) return MGR_OK;
+        ws.t0 = tile_begin;
+        ws.tn = tile_end - tile_begin;
+    }
+    HIP_OK(mgr::launch_unpack_fields(nfields, packed, row_bytes, n, dest, nbins, drop_bin,
+                                     tile_rows, ws, outs, redirect_bin, redirect_srcs,
+                                     (hipStream_t)stream));
+    return MGR_OK;
+}
+
+int mgr_unpack(const void* packed, int64_t row_bytes, int64_t n, const void* dest, int nbins,
+               int drop_bin, int tile_rows, const void* workspace, void* out, int redirect_bin,
+               const void* redirect_src, void* stream) {
+    return mgr_unpack_fields(1, &packed, &row_bytes, n, dest, nbins, drop_bin, tile_rows,
+                             workspace, &out, redirect_bin, redirect_bin >= 0 ? &redirect_src : nullptr,
+                             0, -1, stream);
 }
 
 int mgr_tile_offsets(const void* workspace, int64_t n, int nbins, int tile_rows,

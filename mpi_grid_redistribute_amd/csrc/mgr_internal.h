@@ -98,7 +98,7 @@ int nbits_for(int nbins);
 // Kernel ids for the profiler.
 enum KernelId { K_BIN_COUNT, K_SCAN, K_PACK, K_CELL_IDS, K_BIN_IDS, K_CELLNUM_IDX, K_SYNTH,
                 K_EXCHANGE, K_HALO, K_BIN_FINE, K_COUNT_IDS, K_PACK_FINE, K_PACK_NARROW,
-                K_HALO_PACK, K_ONEPASS, K_ONEPASS_FIELDS, K_NUM_KERNELS };
+                K_HALO_PACK, K_ONEPASS, K_ONEPASS_FIELDS, K_UNPACK, K_NUM_KERNELS };
 const char* kernel_name(int k);
 void prof_begin(hipStream_t s, int k);
 void prof_end(hipStream_t s, int k);
@@ -140,6 +140,12 @@ hipError_t launch_pack_fields(int nf, const void* const* srcs, const int64_t* ro
                               const Workspace& ws, void* const* dsts, int redirect_bin,
                               void* const* reds, hipStream_t s, const uint16_t* ids_src,
                               uint16_t* ids_dst, uint16_t* ids_red);
+// The return path (mgr_unpack.hip): out[r] = packed[slot(r)] for the slots of
+// the pack with the same arguments; reds: redirect_src per field, or nullptr.
+hipError_t launch_unpack_fields(int nf, const void* const* packed, const int64_t* row_bytes,
+                                int64_t n, const void* dest, int nbins, int drop_bin,
+                                int tile_rows, const Workspace& ws, void* const* outs,
+                                int redirect_bin, const void* const* reds, hipStream_t s);
 hipError_t launch_synth_uniform(uint64_t seed, int64_t gid0, int64_t n, int dim,
                                 const double* box, double* pos, void* rec32, hipStream_t s);
 int pack_tile_rows(int64_t row_bytes, int nbins);
@@ -200,6 +206,8 @@ struct Hooks {
     int onepass_poison_tile = -1; // >= 0: the multi-field one-pass tile with that ticket treats
                                   // its look-back as given up (a failed partition)
     int msel_wide = 0;            // 1: the wide multi-selection pack also for 1..3 fields
+    int unpack_kernel = 0;        // unpacks: 0 product choice, 1 generic (wave per tile), 2
+                                  // cooperative single-field (field sets go field by field)
 };
 // The scan kernel's copy of the race-test hooks (kernel argument).
 struct ScanTest {

@@ -60,6 +60,7 @@ int set_hook(const char* key, int64_t v) {
     else if (!strcmp(key, "fields_kernel") && in(0, 3)) h->fields_kernel = (int)v;
     else if (!strcmp(key, "onepass_poison_tile") && in(-1, 1 << 30)) h->onepass_poison_tile = (int)v;
     else if (!strcmp(key, "msel_wide") && in(0, 1)) h->msel_wide = (int)v;
+    else if (!strcmp(key, "unpack_kernel") && in(0, 2)) h->unpack_kernel = (int)v;
     else return -1;
     g_hooks.store(h.get(), std::memory_order_release);
     kept.push_back(std::move(h));

@@ -1,0 +1,363 @@
+// Unpack kernels (gfx950): the return path, the inverse of the packs of
+// mgr_pack.hip.  For the (dest, nbins, drop_bin, tile_rows, workspace,
+// redirect_bin) of a pack, slot(r) is the row at which that pack writes
+// source row r (redist.py:195-199, send_buff[i] = data[rank_to_send == i],
+// order kept -- the permutation being inverted); the unpack writes
+// out[r] = packed[slot(r)] (redirect_src[slot(r)] for a row of redirect_bin,
+// zero bytes for a row of drop_bin).  The slot arithmetic is the pack's own
+// (seg_start, the ballot match and rank of mgr_device.h); nothing is binned
+// or scanned again.  Helpers: mgr_device.h.
+#include "mgr_device.h"
+
+namespace mgr {
+
+constexpr int kUnpackCoopRounds = 16;   // cooperative unpack tiles: <= 1024 rows (one wave a round)
+constexpr long long kSlotMask = (1ll << 62) - 1;   // bit 62 of a slot: read redirect_src
+
+// ---------------------------------------------------------------- generic
+// Mirror of pack_kernel: one wave per tile, per-wave LDS goff/run tables, any
+// row size in W-byte units, 1- or 2-byte destinations.  Per round: ballot
+// match -> rank inside the wave; slot = tile segment start of the bin +
+// running count + rank; the row is copied from its slot to its own place.
+// kWide (rows > 256 B): the wave copies one row at a time, 64 lanes wide.
+template <int W, typename DestT, bool kWide>
+__global__ __launch_bounds__(kBlock) void unpack_kernel(
+    const uint8_t* __restrict__ packed, int64_t upr /* W-units per row */, int64_t n,
+    const DestT* __restrict__ dest, int nb, int nbits, int drop_bin,
+    const int64_t* __restrict__ offsets, const int64_t* __restrict__ bin_starts, int64_t T,
+    int64_t t0, int64_t tn, int tile_rows, int per_wave_lds, uint8_t* __restrict__ out,
+    int redirect_bin, const uint8_t* __restrict__ redirect_src,
+    const uint32_t* __restrict__ scan_err) {
+    using U = typename Unit<W>::T;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int w = threadIdx.x >> 6, lane = lane_id();
+    const int64_t tl = (int64_t)blockIdx.x * (blockDim.x >> 6) + w;
+    if (tl >= tn || scan_failed(scan_err)) return;
+    const int64_t tile = t0 + tl;
+    int64_t* goff = (int64_t*)(smem + w * per_wave_lds);
+    int32_t* run = (int32_t*)(smem + w * per_wave_lds + align16(nb * 8));
+    for (int b = lane; b < nb; b += 64) {
+        goff[b] = seg_start(offsets, bin_starts, T, tile, b, redirect_bin);
+        run[b] = 0;
+    }
+    wave_sync();
+    const int64_t row0 = tile * (int64_t)tile_rows;
+    const int rows = (int)min((int64_t)tile_rows, n - row0);
+    const U* __restrict__ p_u = (const U*)packed;
+    const U* __restrict__ r_u = (const U*)redirect_src;
+    U* __restrict__ o_u = (U*)out;
+    const U zero{};
+    for (int r0 = 0; r0 < rows; r0 += 64) {
+        const bool valid = r0 + lane < rows;
+        const int64_t row = row0 + r0 + lane;
+        const unsigned b = valid ? (unsigned)dest[row] : 0u;
+        const unsigned long long peers = match_bin(b, valid, nbits);
+        const int rk = rank_in(peers);
+        int64_t slot = 0;
+        if (valid) slot = goff[b] + run[b] + rk;
+        wave_sync();
+        if (valid && rk == 0) run[b] += __popcll(peers);
+        const bool live = valid && (int)b != drop_bin;
+        if (!kWide) {
+            if (live) {
+                const U* sp = ((int)b == redirect_bin ? r_u : p_u) + slot * upr;
+                U* dp = o_u + row * upr;
+                int64_t k = 0;
+                for (; k + 4 <= upr; k += 4) {
+                    const U a0 = sp[k], a1 = sp[k + 1], a2 = sp[k + 2], a3 = sp[k + 3];
+                    dp[k] = a0; dp[k + 1] = a1; dp[k + 2] = a2; dp[k + 3] = a3;
+                }
+                for (; k < upr; ++k) dp[k] = sp[k];
+            } else if (valid) {   // a dropped row: zero bytes
+                U* dp = o_u + row * upr;
+                for (int64_t k = 0; k < upr; ++k) dp[k] = zero;
+            }
+        } else {
+            const unsigned long long todo = __ballot(valid);
+            for (int j = 0; j < 64; ++j) {
+                if (!((todo >> j) & 1ull)) continue;
+                const int bj = __shfl((int)b, j, 64);
+                const int64_t sj = __shfl((long long)slot, j, 64);
+                U* dp = o_u + (row0 + r0 + j) * upr;
+                if (bj == drop_bin) {
+                    for (int64_t k = lane; k < upr; k += 64) dp[k] = zero;
+                } else {
+                    const U* sp = (bj == redirect_bin ? r_u : p_u) + sj * upr;
+                    for (int64_t k = lane; k < upr; k += 64) dp[k] = sp[k];
+                }
+            }
+        }
+        wave_sync();
+    }
+}
+
+// ------------------------------------------------------------ cooperative
+// Mirror of pack_coop_kernel / pack_coop_fields_kernel, <= 64 bins and rows
+// of <= 16 units of 4/8/16 bytes: one workgroup per tile, wave w ranks round
+// w (64 rows) -- lane b fetches bin b's tile base, the waves exchange their
+// per-bin counts through a [rounds][64] LDS table behind one barrier -- and
+// moves up to four fields of the round from that ONE ranking.  The moves are
+// unit-transposed: lane l owns units 64 k + l of the round, takes its row's
+// slot by shfl, gathers packed[slot * UPR + part] and stores out[row0 * UPR +
+// 64 k + l], so every store instruction writes 64 * W contiguous bytes; the
+// gathers read a few contiguous runs (same-bin rows of a round hold
+// consecutive slots).  The destination bytes are loaded and waited for
+// first: every gather address depends on them.  A field is U = W * 32 + UPR
+// (0: no field), as the pack's CoopField.
+template <int U>
+struct CoopGather {
+    static constexpr int W = U >> 5, UPR = U & 31;
+    using T = typename Unit<(W ? W : 4)>::T;
+    T v[UPR ? UPR : 1];
+    // tgt: this lane's row's slot (bit 62: in redirect_src), < 0: a dropped row
+    __device__ __forceinline__ void load(const uint8_t* __restrict__ packed,
+                                         const uint8_t* __restrict__ red, long long tgt, int nr,
+                                         int lane) {
+        if constexpr (U != 0) {
+            const T* __restrict__ p_u = (const T*)packed;
+            const T* __restrict__ r_u = (const T*)red;
+#pragma unroll
+            for (int k = 0; k < UPR; ++k) {
+                const int u = 64 * k + lane;
+                const int r = u / UPR, part = u - r * UPR;
+                const long long t = __shfl(tgt, r, 64);
+                v[k] = T{};
+                if (u < nr * UPR && t >= 0) {
+                    const T* s = (t >> 62) ? r_u : p_u;
+                    v[k] = s[(t & kSlotMask) * UPR + part];
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void store(uint8_t* __restrict__ out, int64_t row0, int nr,
+                                          int lane) const {
+        if constexpr (U != 0) {
+            T* __restrict__ o_u = (T*)out + row0 * UPR;
+#pragma unroll
+            for (int k = 0; k < UPR; ++k)
+                if (64 * k + lane < nr * UPR) o_u[64 * k + lane] = v[k];
+        }
+    }
+};
+
+struct UnpackFieldPtrs {
+    const uint8_t* packed[4];
+    const uint8_t* red[4];
+    uint8_t* out[4];
+};
+
+template <int U0, int U1, int U2, int U3>
+__global__ __launch_bounds__(1024) void unpack_coop_kernel(
+    UnpackFieldPtrs fp, int64_t n, const uint8_t* __restrict__ dest, int nb, int nbits,
+    int drop_bin, const int64_t* __restrict__ offsets, const int64_t* __restrict__ bin_starts,
+    int64_t T, int64_t t0, int64_t tn, int tile_rows, int redirect_bin, int xcd,
+    const uint32_t* __restrict__ scan_err) {
+    __shared__ int s_cnt[kUnpackCoopRounds][64];
+    const int w = threadIdx.x >> 6, lane = lane_id();
+    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t row0 = tile * (int64_t)tile_rows + 64 * w;
+    const int nr = (int)max((int64_t)0, min((int64_t)64, n - row0));
+    const unsigned b = lane < nr ? (unsigned)dest[row0 + lane] : 0u;
+    long long tbase = 0;
+    if (lane < nb) tbase = seg_start(offsets, bin_starts, T, tile, lane, redirect_bin);
+    // rank inside the round; lane l counts bin l
+    const bool valid = lane < nr;
+    unsigned long long pe = __ballot(valid), mine = pe;
+    for (int i = 0; i < nbits; ++i) {
+        const unsigned long long m = __ballot((b >> i) & 1u);
+        pe &= ((b >> i) & 1u) ? m : ~m;
+        mine &= ((lane >> i) & 1) ? m : ~m;
+    }
+    if (!valid) pe = 0ull;
+    s_cnt[w][lane] = __popcll(mine);
+    __syncthreads();
+    if (scan_failed(scan_err)) return;
+    for (int j = 0; j < w; ++j) tbase += s_cnt[j][lane];
+    const long long base = __shfl(tbase, (int)b, 64);
+    long long tgt = -1;
+    if (valid && (int)b != drop_bin)
+        tgt = (base + rank_in(pe)) | ((int)b == redirect_bin ? (1ll << 62) : 0ll);
+    CoopGather<U0> f0;
+    CoopGather<U1> f1;
+    CoopGather<U2> f2;
+    CoopGather<U3> f3;
+    f0.load(fp.packed[0], fp.red[0], tgt, nr, lane);
+    f1.load(fp.packed[1], fp.red[1], tgt, nr, lane);
+    f2.load(fp.packed[2], fp.red[2], tgt, nr, lane);
+    f3.load(fp.packed[3], fp.red[3], tgt, nr, lane);
+    f0.store(fp.out[0], row0, nr, lane);
+    f1.store(fp.out[1], row0, nr, lane);
+    f2.store(fp.out[2], row0, nr, lane);
+    f3.store(fp.out[3], row0, nr, lane);
+}
+
+// --------------------------------------------------------------- launchers
+// log2 of the widest copy unit (<= 16 bytes) that divides every address in a
+// (the packs' unit_log rule)
+static inline int unit_log(uintptr_t a) {
+    return (a & 15) == 0 ? 4 : (a & 7) == 0 ? 3 : (a & 3) == 0 ? 2 : (a & 1) == 0 ? 1 : 0;
+}
+
+// A field's cooperative signature W * 32 + UPR -- the widest of 16/8/4 bytes
+// dividing its row and every pointer, <= 16 units per row -- or -1 (the
+// alignment rule of the pack's coop_unit).
+static int coop_unit(const void* packed, int64_t rb, const void* out, const void* red) {
+    uintptr_t a = (uintptr_t)packed | (uintptr_t)out | (uintptr_t)rb;
+    if (red) a |= (uintptr_t)red;
+    const int W = (a & 15) == 0 ? 16 : (a & 7) == 0 ? 8 : (a & 3) == 0 ? 4 : 0;
+    if (!W || rb / W > 16) return -1;
+    return W * 32 + (int)(rb / W);
+}
+
+static bool coop_shape(int nbins, int tile_rows) {
+    return nbins <= 64 && dest_bytes(nbins) == 1 && tile_rows <= 64 * kUnpackCoopRounds;
+}
+
+#define MGR_UCK(A, B, C, D)                                                                    \
+    {                                                                                          \
+        hipLaunchKernelGGL((unpack_coop_kernel<A, B, C, D>), dim3((unsigned)ws.tn),            \
+                           dim3(tile_rows), 0, s, fp, n, (const uint8_t*)dest, nbins,          \
+                           nbits_for(nbins), drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, \
+                           ws.tn, tile_rows, redirect_bin, kXcdPackChunk, ws.scan_err);        \
+        return hipGetLastError();                                                              \
+    }
+
+// One field through the cooperative kernel (hipErrorNotSupported: not its shape).
+static hipError_t unpack_coop(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
+                              int nbins, int drop_bin, int tile_rows, const Workspace& ws,
+                              void* out, int redirect_bin, const void* red, hipStream_t s) {
+    if (!coop_shape(nbins, tile_rows)) return hipErrorNotSupported;
+    const int u = coop_unit(packed, row_bytes, out, red);
+    if (u < 0) return hipErrorNotSupported;
+    UnpackFieldPtrs fp{};
+    fp.packed[0] = (const uint8_t*)packed;
+    fp.red[0] = (const uint8_t*)red;
+    fp.out[0] = (uint8_t*)out;
+#define MGR_UC1(W_, N_) case W_ * 32 + N_: MGR_UCK(W_ * 32 + N_, 0, 0, 0)
+    switch (u) {
+        MGR_UC1(16, 1) MGR_UC1(16, 2) MGR_UC1(16, 3) MGR_UC1(16, 4)
+        MGR_UC1(8, 1) MGR_UC1(8, 2) MGR_UC1(8, 3) MGR_UC1(8, 4)
+        MGR_UC1(8, 5) MGR_UC1(8, 6) MGR_UC1(8, 7) MGR_UC1(8, 8)
+        MGR_UC1(4, 1) MGR_UC1(4, 2) MGR_UC1(4, 3) MGR_UC1(4, 4)
+        MGR_UC1(4, 5) MGR_UC1(4, 6) MGR_UC1(4, 7) MGR_UC1(4, 8)
+        MGR_UC1(4, 9) MGR_UC1(4, 10) MGR_UC1(4, 11) MGR_UC1(4, 12)
+        MGR_UC1(4, 13) MGR_UC1(4, 14) MGR_UC1(4, 15) MGR_UC1(4, 16)
+        default: break;
+    }
+#undef MGR_UC1
+    return hipErrorNotSupported;
+}
+
+// 2..4 fields of a signature pack_coop_fields takes, from one ranking
+// (hipErrorNotSupported otherwise).
+static hipError_t unpack_coop_fields(int nf, const void* const* packed, const int64_t* row_bytes,
+                                     int64_t n, const void* dest, int nbins, int drop_bin,
+                                     int tile_rows, const Workspace& ws, void* const* outs,
+                                     int redirect_bin, const void* const* reds, hipStream_t s) {
+    if (!coop_shape(nbins, tile_rows)) return hipErrorNotSupported;
+    int u[4] = {0, 0, 0, 0};
+    UnpackFieldPtrs fp{};
+    for (int f = 0; f < nf; ++f) {
+        u[f] = coop_unit(packed[f], row_bytes[f], outs[f], reds ? reds[f] : nullptr);
+        if (u[f] < 0) return hipErrorNotSupported;
+        fp.packed[f] = (const uint8_t*)packed[f];
+        fp.red[f] = reds ? (const uint8_t*)reds[f] : nullptr;
+        fp.out[f] = (uint8_t*)outs[f];
+    }
+    auto sig = [&](int a, int b, int c, int d) { return u[0] == a && u[1] == b && u[2] == c && u[3] == d; };
+    constexpr int F4x1 = 4 * 32 + 1, F4x3 = 4 * 32 + 3, F8x1 = 8 * 32 + 1, F8x3 = 8 * 32 + 3,
+                  F16x2 = 16 * 32 + 2, F4x9 = 4 * 32 + 9, F16x1 = 16 * 32 + 1, F8x2 = 8 * 32 + 2;
+    // the field sets of pack_coop_fields (mgr_pack.hip)
+    if (sig(F4x3, F4x3, F4x1, F8x1)) MGR_UCK(F4x3, F4x3, F4x1, F8x1)
+    if (sig(F8x3, F8x1, 0, 0)) MGR_UCK(F8x3, F8x1, 0, 0)
+    if (sig(F16x2, F8x3, 0, 0)) MGR_UCK(F16x2, F8x3, 0, 0)
+    if (sig(F4x9, F4x3, 0, 0)) MGR_UCK(F4x9, F4x3, 0, 0)
+    if (sig(F4x3, F8x1, 0, 0)) MGR_UCK(F4x3, F8x1, 0, 0)
+    if (sig(F16x1, F8x1, 0, 0)) MGR_UCK(F16x1, F8x1, 0, 0)
+    if (sig(F8x3, F8x3, F8x1, 0)) MGR_UCK(F8x3, F8x3, F8x1, 0)
+    if (sig(F4x3, F4x3, F8x1, 0)) MGR_UCK(F4x3, F4x3, F8x1, 0)
+    if (sig(F8x2, F8x1, 0, 0)) MGR_UCK(F8x2, F8x1, 0, 0)
+    return hipErrorNotSupported;
+}
+#undef MGR_UCK
+
+template <int W, typename DestT, bool kWide>
+static hipError_t unpack_t(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
+                           int nb, int drop_bin, int tile_rows, const Workspace& ws, void* out,
+                           int redirect_bin, const void* red, hipStream_t s) {
+    auto k = unpack_kernel<W, DestT, kWide>;
+    const int per_wave = align16(nb * 8) + align16(nb * 4);
+    const int wpb = waves_per_block(per_wave);
+    const int lds = per_wave * wpb;
+    ensure_lds(k, lds);
+    const int64_t grid = (ws.tn + wpb - 1) / wpb;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * wpb), (size_t)lds, s,
+                       (const uint8_t*)packed, row_bytes / W, n, (const DestT*)dest, nb,
+                       nbits_for(nb), drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn,
+                       tile_rows, per_wave, (uint8_t*)out, redirect_bin, (const uint8_t*)red,
+                       ws.scan_err);
+    return hipGetLastError();
+}
+
+template <int W>
+static hipError_t unpack_w(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
+                           int nb, int drop_bin, int tile_rows, const Workspace& ws, void* out,
+                           int redirect_bin, const void* red, hipStream_t s) {
+    const bool wide = row_bytes > 256;
+    if (dest_bytes(nb) == 1)
+        return wide ? unpack_t<W, uint8_t, true>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s)
+                    : unpack_t<W, uint8_t, false>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+    return wide ? unpack_t<W, uint16_t, true>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s)
+                : unpack_t<W, uint16_t, false>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+}
+
+// One field: the cooperative kernel where it takes the shape (hook
+// unpack_kernel 1: never), else the generic one in the widest unit dividing
+// the row and every base address.
+static hipError_t unpack_rows(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
+                              int nbins, int drop_bin, int tile_rows, const Workspace& ws,
+                              void* out, int redirect_bin, const void* red, hipStream_t s,
+                              const Hooks& h) {
+    if (redirect_bin < 0) red = nullptr;
+    if (h.unpack_kernel != 1) {
+        const hipError_t e = unpack_coop(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows,
+                                         ws, out, redirect_bin, red, s);
+        if (e != hipErrorNotSupported) return e;
+    }
+    uintptr_t a = (uintptr_t)packed | (uintptr_t)out | (uintptr_t)row_bytes;
+    if (red) a |= (uintptr_t)red;
+    switch (unit_log(a)) {
+        case 4: return unpack_w<16>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+        case 3: return unpack_w<8>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+        case 2: return unpack_w<4>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+        case 1: return unpack_w<2>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+        default: return unpack_w<1>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+    }
+}
+
+// mgr_unpack_fields: 2..4 fields of a cooperative signature move from one
+// ranking in one launch (hook unpack_kernel 0 only); any other set goes
+// field by field through the single-field kernels with the same dest.
+hipError_t launch_unpack_fields(int nf, const void* const* packed, const int64_t* row_bytes,
+                                int64_t n, const void* dest, int nbins, int drop_bin,
+                                int tile_rows, const Workspace& ws, void* const* outs,
+                                int redirect_bin, const void* const* reds, hipStream_t s) {
+    if (n <= 0 || ws.tn <= 0) return hipSuccess;
+    const Hooks& h = hooks();   // one snapshot for the whole launch
+    if (redirect_bin < 0) reds = nullptr;
+    prof_begin(s, K_UNPACK);
+    hipError_t e = hipErrorNotSupported;
+    if (nf >= 2 && nf <= 4 && h.unpack_kernel == 0)
+        e = unpack_coop_fields(nf, packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws,
+                               outs, redirect_bin, reds, s);
+    if (e == hipErrorNotSupported) {
+        e = hipSuccess;
+        for (int f = 0; f < nf && e == hipSuccess; ++f)
+            e = unpack_rows(packed[f], row_bytes[f], n, dest, nbins, drop_bin, tile_rows, ws,
+                            outs[f], redirect_bin, reds ? reds[f] : nullptr, s, h);
+    }
+    prof_end(s, K_UNPACK);
+    return e;
+}
+
+}  // namespace mgr

@@ -11,6 +11,11 @@ redistribution does:
                           the output at its source-ordered slot;
   4. row exchange      -> peers' segments land in place: no unpack pass.
 Steps 1, 2 and 4 are device-agnostic (CPU tensors + gloo in the tests).
+
+The return path (exchange_back) runs the same layout backwards: the rows a
+rank received go back to their sources with the two sides' counts and
+offsets swapped -- no count exchange, no host read -- and an unpack callback
+puts every returned row back onto its source row.
 """
 from __future__ import annotations
 
@@ -178,6 +183,50 @@ def exchange(transport, row_bytes, bin_counts, rank, device, pack, extra_rows=No
                             lay.recv_offsets)
     transport.note_rows(row_bytes, sc, rc)
     return outs, lay
+
+
+def exchange_back(transport, row_bytes, layout, values, rank, device, unpack_all, scratch=None):
+    """The forward exchange of ``layout`` (an ExchangeLayout of exchange() or
+    exchange_pipelined()) run backwards for per-row results.  ``values``: per
+    field a flat uint8 tensor of layout.total_recv rows of row_bytes[f] (any
+    row size, unrelated to what went forward), in the order the forward call
+    delivered its rows.  The rows received from source s (rows
+    [recv_offsets[s], + recv_counts[s]) of every field) go back to s; the rows
+    sent to p come back into a staging buffer of layout.total_send rows at
+    send_offsets[p] (``scratch("back{f}", nbytes)``, else fresh) -- the
+    transport's exchange_rows with the two sides' counts and offsets swapped,
+    one message group.  The layout holds every size: no count exchange, no
+    host read.  With layout.redirect_self the self rows never travel (both
+    self counts are zero) and the unpack reads them from ``values`` in place.
+    ``unpack_all(stagings, values, redirect_bin, value_offsets)`` (redirect_bin
+    = rank or -1, value_offsets[f] = the byte offset of the self rows in
+    values[f]) moves every row to its source row and returns the outputs,
+    which exchange_back returns.  Off-rank bytes are noted in the transport's
+    Traffic: the forward call's with the directions swapped."""
+    row_bytes = [int(b) for b in row_bytes]
+    lay = layout
+    sc = np.array(lay.recv_counts, dtype=np.int64)    # what this rank sends back
+    rc = np.array(lay.send_counts, dtype=np.int64)    # what comes back to it
+    if lay.redirect_self:
+        sc[rank] = 0
+        rc[rank] = 0
+    stagings = []
+    for f, rb in enumerate(row_bytes):
+        nbytes = max(lay.total_send * rb, 1)
+        stagings.append(scratch(f"back{f}", nbytes) if scratch is not None
+                        else torch.empty(nbytes, dtype=torch.uint8, device=device))
+    transport.exchange_rows(list(values), stagings, row_bytes, sc, lay.recv_offsets, rc,
+                            lay.send_offsets)
+    if not lay.redirect_self and transport.skips_self and lay.send_counts[rank]:
+        # a transport that leaves the self segment alone, on a layout that packed it
+        for f, rb in enumerate(row_bytes):
+            a, b = int(lay.send_offsets[rank]) * rb, int(lay.recv_offsets[rank]) * rb
+            k = int(lay.send_counts[rank]) * rb
+            stagings[f][a:a + k].copy_(values[f][b:b + k])
+    transport.note_rows(row_bytes, sc, rc)
+    redirect = rank if lay.redirect_self else -1
+    offs = [int(lay.recv_offsets[rank]) * rb if lay.redirect_self else 0 for rb in row_bytes]
+    return unpack_all(stagings, list(values), redirect, offs)
 
 
 _COMM_STREAMS = OrderedDict()

@@ -39,7 +39,8 @@ import torch
 from . import _lib
 from ._arrays import Positions, Rows, box_dtype_code, device, id_array, pos_code
 from .comm import SelfComm, as_transport
-from .exchange import check_counts, exchange, exchange_pipelined, host_read_start, host_read_wait
+from .exchange import (check_counts, exchange, exchange_back, exchange_pipelined, host_read_start,
+                       host_read_wait)
 from .halo import DeviceSelect, exchange_overload, halo_capacity, thresholds
 
 
@@ -335,6 +336,11 @@ class Scratch:
             b = self.bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         return b
 
+    def take(self, name):
+        """Remove and return the current stream's buffer ``name`` (None if there
+        is none): the caller owns it, and the next get() allocates anew."""
+        return self.bufs.pop((name, self._stream_key()), None)
+
     def release(self):
         self.bufs.clear()
         self.streams.clear()
@@ -356,6 +362,45 @@ def _scratch(n, nbins, max_row_bytes, dev, cache=None, dest=True, tag="", tile_r
     ws = torch.empty(int(wsb), dtype=torch.uint8, device=dev)
     d = torch.empty(db, dtype=torch.uint8, device=dev) if dest else None
     return tile_rows, ws, d
+
+
+class Route:
+    """What ``return_to_source`` needs to send per-row results back along a
+    redistribution (``return_route=True``): the rows' destination bytes, the
+    workspace as the scan left it (every (bin, tile) segment start), the tile
+    size, bin count and drop bin, and the exchange's layout.  The two device
+    buffers are TAKEN OUT of the redistributor's scratch -- no copy; the next
+    call on the redistributor allocates a new workspace and destination array
+    -- so a route stays valid across later calls and may be used any number
+    of times.  Memory per live route: about n_source * mgr_dest_bytes(nbins) +
+    mgr_workspace_bytes(n_source, nbins, tile_rows) bytes (1-2 bytes per row
+    plus 12 bytes per (bin, tile)), freed by ``release()``."""
+
+    def __init__(self, owner, dest, ws, tile_rows, nbins, drop_bin, n_source, layout):
+        self._owner = owner
+        self._dest, self._ws = dest, ws
+        self.tile_rows, self.nbins, self.drop_bin = int(tile_rows), int(nbins), int(drop_bin)
+        self.n_source = int(n_source)
+        self.n_local = int(layout.total_recv)
+        self.layout = layout
+
+    @property
+    def send_counts(self):
+        """Rows the forward call sent to every rank (host int64, a copy)."""
+        return self.layout.send_counts.copy()
+
+    @property
+    def recv_counts(self):
+        """Rows the forward call received from every rank (host int64, a copy)."""
+        return self.layout.recv_counts.copy()
+
+    @property
+    def released(self):
+        return self._ws is None
+
+    def release(self):
+        """Free the route's device memory; it cannot be used afterwards."""
+        self._dest = self._ws = None
 
 
 def exchange_chunks_for(size, row_bytes):
@@ -474,7 +519,7 @@ class MPIGridRedistributor:
 
     # ------------------------------------------------- redistribution (L2)
     def redistribute_by_position(self, data, position, periodic=True, overload_lengths=None,
-                                 return_positions=False, fine_cells=None):
+                                 return_positions=False, fine_cells=None, return_route=False):
         """redist.py:115-166.  Returns the rows of ``data`` whose position
         falls in this rank's cell, from every rank, in source-rank order;
         ``position`` is wrapped in place when periodic (S1).  ``data`` may be
@@ -489,7 +534,15 @@ class MPIGridRedistributor:
         of the plain result, computed from fine cells binned at the source.
         ``return_positions``: (data, positions) -- (data, [positions,]
         offsets) with ``fine_cells``; ``data`` is the tuple of fields for a
-        SoA payload."""
+        SoA payload.  ``return_route``: (result, route) -- ``result`` is what
+        the call returns otherwise, ``route`` a Route for ``return_to_source``
+        (not with ``overload_lengths``: halo rows are copies, their return is
+        a reduction; not with ``fine_cells``: a second permutation)."""
+        if return_route and (overload_lengths is not None or fine_cells is not None):
+            raise NotImplementedError(
+                "return_route together with overload_lengths or fine_cells: halo rows are "
+                "copies (their return is a reduction onto the owners) and the fine-cell sort "
+                "adds a second permutation; neither has a return path")
         fields, multi = _payload(data, self._dev)
         for d in (data if multi else [data]):
             self._check_host_alias(d, position)
@@ -531,8 +584,62 @@ class MPIGridRedistributor:
         outs, m = self._run(run_fields, binner, n, drop=False, row_bytes_hint=row_bytes_hint)
         res = _results(fields, outs[:nd], m, multi)
         if return_positions:
-            return res, run_fields[nd].wrap(outs[nd], m)
-        return res
+            res = res, run_fields[nd].wrap(outs[nd], m)
+        return (res, self._take_route()) if return_route else res
+
+    def _take_route(self):
+        """The Route of the _run just made: its destination bytes and
+        workspace leave the scratch (Route)."""
+        tile_rows, nb, drop_bin, n = self._last_run
+        ws, dest = self._scratch.take("ws"), self._scratch.take("dest")
+        return Route(self, dest, ws, tile_rows, nb, drop_bin, n, self._last_layout)
+
+    def return_to_source(self, values, route):
+        """The inverse of the redistribution that made ``route``: ``values``
+        -- one array, or a tuple / list of up to MAX_FIELDS arrays, of
+        ``route.n_local`` rows each, of any dtype and trailing shape (per-row
+        results computed on the owning rank: forces, densities, tags ...) --
+        go back to the ranks and rows they came from.  Returns arrays of
+        ``route.n_source`` rows in the container of ``values`` (numpy in,
+        numpy out; GPU torch in, GPU torch out): row i is the value computed
+        for the call's original row i; a row ``redistribute_by_cell_number``
+        dropped is zero.  One reverse row exchange (exchange_back: the forward
+        messages with sender and receiver swapped, no count exchange, no host
+        sync) and one mgr_unpack_fields call; nothing is binned or scanned
+        again."""
+        if not isinstance(route, Route):
+            raise TypeError("route: a Route of redistribute_by_position(..., return_route=True)")
+        if route.released:
+            raise ValueError("the route was released")
+        o = route._owner
+        if o is not self and (o.size != self.size or o.rank != self.rank
+                              or not np.array_equal(o.grid_topology, self.grid_topology)
+                              or not np.array_equal(o.box_length, self.box_length)):
+            raise ValueError("the route was made by another redistributor (different size, "
+                             "rank or plan)")
+        fields, multi = _payload(values, self._dev)
+        for i, f in enumerate(fields):
+            if f.n != route.n_local:
+                raise ValueError(f"values field {i} has {f.n} rows, the route delivered "
+                                 f"{route.n_local}")
+        self.comm.reset_traffic()
+        n, stream = route.n_source, _lib.stream_handle()
+        rbs = [f.row_bytes for f in fields]
+
+        def unpack_all(stagings, vals, redirect_bin, offs):
+            outs = [torch.empty(max(n * rb, 1), dtype=torch.uint8, device=self._dev)
+                    for rb in rbs]
+            # an empty field has no address: no row reads it, any pointer serves
+            reds = [(v.data_ptr() or s.data_ptr()) + o for v, s, o in zip(vals, stagings, offs)]
+            _lib.call("mgr_unpack_fields", len(rbs), _ptrs([s.data_ptr() for s in stagings]),
+                      _i64s(rbs), n, _lib.ptr(route._dest), route.nbins, route.drop_bin,
+                      route.tile_rows, _lib.ptr(route._ws), _ptrs([t.data_ptr() for t in outs]),
+                      redirect_bin, _ptrs(reds) if redirect_bin >= 0 else None, 0, -1, stream)
+            return outs
+
+        outs = exchange_back(self.comm, rbs, route.layout, [f.flat for f in fields], self.rank,
+                             self._dev, unpack_all, scratch=self._scratch.get)
+        return _results(fields, outs, n, multi)
 
     def _redistribute_halo(self, data, position, rows, pos, periodic, overload_lengths,
                            return_positions):
@@ -721,11 +828,13 @@ class MPIGridRedistributor:
     def _pos_row_bytes(position, pos):
         return int(position.shape[1]) * _lib.POS_ITEMSIZE[pos.code]
 
-    def redistribute_by_cell_number(self, data, rank_to_send):
+    def redistribute_by_cell_number(self, data, rank_to_send, return_route=False):
         """redist.py:169-200: send row i to rank ``rank_to_send[i]``; ids
         outside [0, size) are dropped (S6).  ``data``: one array or a tuple /
         list of arrays sharing axis 0 (SoA), all sent with the same ids in one
-        pass; the result is then a tuple in the same order."""
+        pass; the result is then a tuple in the same order.  ``return_route``:
+        (result, route) for ``return_to_source``, where a dropped row comes
+        back as zero bytes."""
         self.comm.reset_traffic()
         fields, multi = _payload(data, self._dev)
         n = fields[0].n
@@ -738,7 +847,8 @@ class MPIGridRedistributor:
                       tile_rows, _lib.ptr(ws), _lib.stream_handle())
 
         outs, m = self._run(fields, binner, n, drop=True)
-        return _results(fields, outs, m, multi)
+        res = _results(fields, outs, m, multi)
+        return (res, self._take_route()) if return_route else res
 
     def _run(self, fields, binner, n, drop, row_bytes_hint=None, extra_rows=None, side=None,
              deferred=None):
@@ -756,6 +866,7 @@ class MPIGridRedistributor:
         tile_rows, ws, dest = _scratch(n, nb, _tile_hint(hint, side), self._dev,
                                        self._scratch)
         binner(dest, tile_rows, ws)
+        self._last_run = (tile_rows, nb, P if drop else -1, n)
         stream = _lib.stream_handle()
         bin_counts = torch.empty(nb, dtype=torch.int64, device=self._dev)
         _lib.call("mgr_scan", n, nb, tile_rows, _lib.ptr(ws), _lib.ptr(bin_counts), stream)
@@ -920,6 +1031,7 @@ class GridPartitioner:
         (out_flat, fine_ids_out, bin_counts)."""
         n = int(pos_tensor.shape[0])
         tile_rows, ws, dest, out, counts = self.buffers(n, row_bytes)
+        self._last_part = (int(n), int(row_bytes))
         self.last_counts = counts   # device bin counts of the last device call
         code = pos_code(pos_tensor.dtype)
         s = _lib.stream_handle(stream)
@@ -964,6 +1076,7 @@ class GridPartitioner:
             counts = torch.empty(self.nbins, dtype=torch.int64, device=self._dev)
             self._cache = {key: (tile_rows, ws, dest, outs, counts)}
         tile_rows, ws, dest, outs, counts = self._cache[key]
+        self._last_part = key
         self.last_counts = counts
         code = pos_code(pos_tensor.dtype)
         s = _lib.stream_handle(stream)
@@ -986,6 +1099,40 @@ class GridPartitioner:
         if fine_cells is None:
             return outs, counts
         return outs, fid_out.view(torch.int16)[:n], counts
+
+    def unpartition_device(self, packed_flat, row_bytes, stream=None):
+        """The return path of ``partition_device`` / ``partition_fields_device``
+        (mgr_unpack): ``packed_flat`` (uint8 device tensor of n * row_bytes, any
+        row size) holds one row per row of the last partition's OUTPUT order;
+        returns out_flat, the same rows in the partition's INPUT order
+        (out[r] = packed[slot(r)]).  Uses the destination bytes and workspace
+        that partition call left in its cache: valid until the next partition
+        call, RuntimeError before any.  The returned buffer is reused by the
+        next call of the same shape."""
+        return self.unpartition_fields_device([packed_flat], [row_bytes], stream)[0]
+
+    def unpartition_fields_device(self, flats, row_bytes, stream=None):
+        """``unpartition_device`` of a SoA set: one mgr_unpack_fields launch."""
+        key = getattr(self, "_last_part", None)
+        ent = self._cache.get(key) if key is not None else None
+        if ent is None:
+            raise RuntimeError("unpartition: no partition_device / partition_fields_device call "
+                               "whose destination bytes and workspace are still cached")
+        n = key[1] if key[0] == "fields" else key[0]
+        tile_rows, ws, dest = ent[0], ent[1], ent[2]
+        rbs = [int(b) for b in row_bytes]
+        for t, rb in zip(flats, rbs):
+            if t.numel() != n * rb:
+                raise ValueError(f"a field of {t.numel()} bytes for {n} rows of {rb}")
+        okey = (n, tuple(rbs))
+        if getattr(self, "_unpart", (None,))[0] != okey:
+            self._unpart = (okey, [torch.empty(max(n * rb, 1), dtype=torch.uint8,
+                                               device=self._dev) for rb in rbs])
+        outs = self._unpart[1]
+        _lib.call("mgr_unpack_fields", len(rbs), _ptrs([t.data_ptr() for t in flats]), _i64s(rbs),
+                  n, _lib.ptr(dest), self.nbins, -1, tile_rows, _lib.ptr(ws),
+                  _ptrs([o.data_ptr() for o in outs]), -1, None, 0, -1, _lib.stream_handle(stream))
+        return outs
 
     def partition_onepass_device(self, data_flat, row_bytes, pos_tensor, periodic=True,
                                  stream=None, fine_cells=None, cap_rows=None):
@@ -1316,4 +1463,5 @@ def mpi_grid_redistribute(data, pos, grid_topology, box_lengths, comm, overload_
                                            periodic=periodic)
 
 
-__all__ = ["MPIGridRedistributor", "GridPartitioner", "mpi_grid_redistribute", "SelfComm"]
+__all__ = ["MPIGridRedistributor", "GridPartitioner", "Route", "mpi_grid_redistribute",
+           "SelfComm"]
