@@ -14,6 +14,7 @@ import torch
 
 from oracle import c_oracle
 from tests import golden_io as G
+from tests.edge_positions import variant_hooks
 from tests.fake_mpi import run_ranks
 
 pytestmark = pytest.mark.gpu
@@ -48,12 +49,8 @@ VARIANTS = [
 def variant(request):
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
-    for k, v in request.param.items():
-        if k != "write_back":
-            _lib.test_hook(k, v)
-    yield request.param
-    for k, v in _lib.HOOK_DEFAULTS.items():
-        _lib.test_hook(k, v)
+    with variant_hooks(_lib, request.param):
+        yield request.param
 
 
 def _wb(obj, variant):
