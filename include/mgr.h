@@ -307,6 +307,32 @@ int mgr_rank_ids(const uint16_t* ids, int64_t n, int nbins, int tile_rows, uint1
 int mgr_pack_ranked(const void* src, int64_t row_bytes, int64_t n, const uint16_t* ids,
                     const uint16_t* ranks, const uint16_t* tile_starts, int nbins, int tile_rows,
                     const void* workspace, void* dst, void* stream);
+/* The way back through the fine-cell sort: the inverse of mgr_pack_ranked.
+ * For the (ids, ranks, tile_starts, nbins, tile_rows, workspace) of a
+ * mgr_rank_ids + mgr_scan pair, mgr_pack_ranked writes row r -- row r of tile
+ * t = r / tile_rows, of fine cell b = min(ids[r], nbins - 1) -- at
+ *     slot(r) = offsets[b * T + t] - tile_starts[t * nbins + b] + ranks[r]
+ * (offsets: the scan's (bin, tile) segment starts in the workspace, T the
+ * tile count).  mgr_unpack_ranked_fields writes
+ *     outs[f][r] = sorted[f][slot(r)]
+ * for every row r and every field f (1..MGR_MAX_FIELDS fields in ONE launch:
+ * a tile's ids, ranks and per-cell bases are read once for all of them).  The
+ * rows of sorted[f] are any row_bytes[f] >= 1, unrelated to what the sort
+ * moved (the <= 64 B, multiple-of-4 limit of mgr_pack_ranked does not apply):
+ * per-row results computed in sorted order, brought back to the order before
+ * the sort.  Rows move in the widest unit of 16/8/4/2/1 bytes dividing
+ * row_bytes[f] and both of the field's addresses.
+ * ids, ranks, tile_starts and workspace must be as mgr_rank_ids and mgr_scan
+ * left them; they are only read: no ranking, no scan, no allocation, no host
+ * sync, stream-ordered.  After a failed scan nothing is written (as the
+ * packs).  outs[f] must not alias any sorted[g].  MGR_EINVAL: nfields outside
+ * 1..MGR_MAX_FIELDS; for n > 0 a null ids, ranks, tile_starts, workspace,
+ * sorted[f] or outs[f]; row_bytes[f] < 1; tile_rows not 2048 or 4096; nbins
+ * outside 1..1024; n < 0.  n == 0: MGR_OK, nothing is read.                */
+int mgr_unpack_ranked_fields(int nfields, const void* const* sorted, const int64_t* row_bytes,
+                             int64_t n, const uint16_t* ids, const uint16_t* ranks,
+                             const uint16_t* tile_starts, int nbins, int tile_rows,
+                             const void* workspace, void* const* outs, void* stream);
 
 /* One call = bin_count + scan + pack of one field: the 1-GPU local stage
  * (bin + scan + stable pack, BASELINE config 2).  bin_offsets: int64

@@ -41,7 +41,8 @@ extern "C" {
  * "unpack_kernel" (mgr_unpack*: 0 the product's choice, 1 the generic
  * wave-per-tile kernel for every shape, 2 the cooperative single-field kernel
  * where it takes a field -- a field set then goes field by field instead of
- * through the multi-field launch).
+ * through the multi-field launch; mgr_unpack_ranked_fields: 1 the run-time
+ * field table also for the templated signatures).
  * Each call publishes a new immutable
  * snapshot of every hook (the library's launches read one snapshot each);
  * < 0 for an unknown key or an out-of-range value.                         */
@@ -62,7 +63,9 @@ int mgr_test_pos_modes(int pos_dtype, int box_dtype, int* wrap, int* quot);
  * (mgr_bin_count_fine), "count_ids" (mgr_count_ids, mgr_rank_ids),
  * "pack_fine" (the 65..1024-bin and ranked packs), "pack_narrow" (rows < 4
  * bytes), "halo_pack" (mgr_msel_pack*), "onepass" (mgr_partition_onepass),
- * "onepass_fields" (mgr_partition_onepass_fields), "unpack" (mgr_unpack*)) or of the RCCL grouped row exchange
+ * "onepass_fields" (mgr_partition_onepass_fields), "unpack" (mgr_unpack,
+ * mgr_unpack_fields), "unpack_ranked" (mgr_unpack_ranked_fields)) or of the
+ * RCCL grouped row exchange
  * ("exchange").  mgr_profile_select: bit k of mask times kernel id k
  * (mgr_profile_kernel_id), default all.                                    */
 int mgr_profile_enable(int on);

@@ -61,6 +61,7 @@ SIGNATURES = {
                              _I64, _P]),
     "mgr_unpack": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
     "mgr_unpack_fields": (_I, [_I, _P, _P, _I64, _P, _I, _I, _I, _P, _P, _I, _P, _I64, _I64, _P]),
+    "mgr_unpack_ranked_fields": (_I, [_I, _P, _P, _I64, _P, _P, _P, _I, _I, _P, _P, _P]),
     "mgr_tile_offsets": (_I, [_P, _I64, _I, _I, _P, _I, _P, _P]),
     "mgr_partition_by_position": (_I, [_P, _P, _I, _I64, _I64, _I, _P, _I64, _P, _P, _P, _I,
                                        _P, _P]),
@@ -207,7 +208,7 @@ HOOK_DEFAULTS = {"tile_rounds": 0, "scan_chunk": 2048, "scan_max_chunks": 1024,
 # Profiler kernel names (mgr_internal.h KernelId).
 PROFILE_KERNELS = ("bin_count", "scan", "pack", "cell_ids", "bin_ids", "cellnum_idx", "synth",
                    "exchange", "halo", "bin_fine", "count_ids", "pack_fine", "pack_narrow",
-                   "halo_pack", "onepass", "onepass_fields", "unpack")
+                   "halo_pack", "onepass", "onepass_fields", "unpack", "unpack_ranked")
 
 
 _prof_on = False

@@ -99,7 +99,8 @@ const char* kernel_name(int k) {
                                                "bin_ids", "cellnum_idx", "synth",
                                                "exchange", "halo", "bin_fine", "count_ids",
                                                "pack_fine", "pack_narrow", "halo_pack",
-                                               "onepass", "onepass_fields", "unpack"};
+                                               "onepass", "onepass_fields", "unpack",
+                                               "unpack_ranked"};
     return (k >= 0 && k < K_NUM_KERNELS) ? names[k] : "?";
 }
 
@@ -819,6 +820,30 @@ int mgr_unpack(const void* packed, int64_t row_bytes, int64_t n, const void* des
     return mgr_unpack_fields(1, &packed, &row_bytes, n, dest, nbins, drop_bin, tile_rows,
                              workspace, &out, redirect_bin, redirect_bin >= 0 ? &redirect_src : nullptr,
                              0, -1, stream);
+}
+
+int mgr_unpack_ranked_fields(int nfields, const void* const* sorted, const int64_t* row_bytes,
+                             int64_t n, const uint16_t* ids, const uint16_t* ranks,
+                             const uint16_t* tile_starts, int nbins, int tile_rows,
+                             const void* workspace, void* const* outs, void* stream) {
+    if (nfields < 1 || nfields > MGR_MAX_FIELDS)
+        return fail(MGR_EINVAL, "nfields %d not in [1, %d]", nfields, MGR_MAX_FIELDS);
+    if (!sorted || !row_bytes || !outs) return fail(MGR_EINVAL, "null field arrays");
+    if (tile_rows != 2048 && tile_rows != 4096)
+        return fail(MGR_EINVAL, "tile_rows %d: 2048 or 4096 (mgr_ranked_tile_rows)", tile_rows);
+    if (nbins < 1 || nbins > 1024) return fail(MGR_EINVAL, "nbins %d not in [1, 1024]", nbins);
+    if (n < 0) return fail(MGR_EINVAL, "n < 0");
+    for (int f = 0; f < nfields; ++f) {
+        if (row_bytes[f] < 1) return fail(MGR_EINVAL, "field %d: row_bytes %lld", f, (long long)row_bytes[f]);
+        if (n > 0 && (!sorted[f] || !outs[f])) return fail(MGR_EINVAL, "field %d: null sorted/out", f);
+    }
+    if (n == 0) return MGR_OK;
+    if (!ids || !ranks || !tile_starts || !workspace)
+        return fail(MGR_EINVAL, "null ids/ranks/tile_starts/workspace");
+    const mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
+    HIP_OK(mgr::launch_unpack_ranked_fields(nfields, sorted, row_bytes, n, ids, ranks, tile_starts,
+                                            nbins, tile_rows, ws, outs, (hipStream_t)stream));
+    return MGR_OK;
 }
 
 int mgr_tile_offsets(const void* workspace, int64_t n, int nbins, int tile_rows,

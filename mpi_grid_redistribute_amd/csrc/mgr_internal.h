@@ -98,7 +98,7 @@ int nbits_for(int nbins);
 // Kernel ids for the profiler.
 enum KernelId { K_BIN_COUNT, K_SCAN, K_PACK, K_CELL_IDS, K_BIN_IDS, K_CELLNUM_IDX, K_SYNTH,
                 K_EXCHANGE, K_HALO, K_BIN_FINE, K_COUNT_IDS, K_PACK_FINE, K_PACK_NARROW,
-                K_HALO_PACK, K_ONEPASS, K_ONEPASS_FIELDS, K_UNPACK, K_NUM_KERNELS };
+                K_HALO_PACK, K_ONEPASS, K_ONEPASS_FIELDS, K_UNPACK, K_UNPACK_RANKED, K_NUM_KERNELS };
 const char* kernel_name(int k);
 void prof_begin(hipStream_t s, int k);
 void prof_end(hipStream_t s, int k);
@@ -146,6 +146,13 @@ hipError_t launch_unpack_fields(int nf, const void* const* packed, const int64_t
                                 int64_t n, const void* dest, int nbins, int drop_bin,
                                 int tile_rows, const Workspace& ws, void* const* outs,
                                 int redirect_bin, const void* const* reds, hipStream_t s);
+// The way back through the fine-cell sort (mgr_unpack.hip): outs[f][r] =
+// sorted[f][slot(r)] for the slots of mgr_pack_ranked with the same ids, ranks,
+// tile_starts and workspace.
+hipError_t launch_unpack_ranked_fields(int nf, const void* const* sorted, const int64_t* row_bytes,
+                                       int64_t n, const uint16_t* ids, const uint16_t* ranks,
+                                       const uint16_t* tile_starts, int nbins, int tile_rows,
+                                       const Workspace& ws, void* const* outs, hipStream_t s);
 hipError_t launch_synth_uniform(uint64_t seed, int64_t gid0, int64_t n, int dim,
                                 const double* box, double* pos, void* rec32, hipStream_t s);
 int pack_tile_rows(int64_t row_bytes, int nbins);

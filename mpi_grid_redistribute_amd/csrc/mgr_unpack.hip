@@ -360,4 +360,204 @@ hipError_t launch_unpack_fields(int nf, const void* const* packed, const int64_t
     return e;
 }
 
+// ------------------------------------------------------------------ ranked
+// Inverse of pack_ranked_kernel (mgr_unpack_ranked_fields): the fine-cell sort
+// places row r of tile t, bin b at
+//     slot(r) = offsets[b * T + t] - tile_starts[t * nb + b] + ranks[r]
+// (the pack's gaddr[b] + lpos * RB), so the way back needs no ranking, no
+// ballots and no scan: one 256-thread workgroup per forward tile puts base[b]
+// = offsets[b * T + t] - tile_starts[t * nb + b] into LDS as int64 (<= 8 KiB,
+// one barrier), then wave w walks the 64-row rounds w, w + 4, ...: ids and
+// ranks are loaded coalesced, once for every field, lane l's slot is base[id]
+// + rank, and every field is moved unit-transposed as CoopGather does (lane l
+// owns units 64 k + l of the round and takes its row's slot by shfl), so a
+// store instruction writes 64 * W contiguous bytes of outs[f].  8 KiB of LDS
+// and four waves: up to eight workgroups per CU.
+//
+// Fields: a set of <= 4 fields whose signatures (CoopGather's W * 32 + UPR)
+// are template arguments moves with compile-time unit counts; any other set
+// -- up to MGR_MAX_FIELDS fields, any row size -- moves in the same single
+// launch from the run-time table RankedFields: per field the unit width
+// (16/8/4/2/1 bytes), the units per row and, for rows of <= 64 units, the
+// multiplier that replaces the division unit -> row; rows of more units go a
+// row at a time, 64 lanes wide (unpack_kernel's kWide).
+struct RankedFields {
+    const uint8_t* src[MGR_MAX_FIELDS];
+    uint8_t* out[MGR_MAX_FIELDS];
+    int64_t upr[MGR_MAX_FIELDS];      // units per row
+    uint32_t magic[MGR_MAX_FIELDS];   // ceil(2^20 / upr): u / upr == (u * magic) >> 20, u < 4096, upr <= 64
+    uint8_t wlog[MGR_MAX_FIELDS];     // log2 of the unit's bytes
+    int nf;
+};
+
+template <int W>
+__device__ __forceinline__ void ranked_move(const uint8_t* __restrict__ src,
+                                            uint8_t* __restrict__ out, int64_t upr64,
+                                            uint32_t magic, long long slot, int64_t row0, int nr,
+                                            int lane) {
+    using U = typename Unit<W>::T;
+    const U* __restrict__ s_u = (const U*)src;
+    if (upr64 <= 64) {
+        const int upr = (int)upr64, total = nr * upr;
+        U* __restrict__ o_u = (U*)out + row0 * upr;
+        for (int k0 = 0; 64 * k0 < total; k0 += 4) {
+            U v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int u = 64 * (k0 + j) + lane;
+                const int r = (int)(((uint32_t)u * magic) >> 20);
+                const int part = u - r * upr;
+                const long long t = __shfl(slot, r & 63, 64);
+                v[j] = U{};
+                if (u < total) v[j] = s_u[t * upr + part];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int u = 64 * (k0 + j) + lane;
+                if (u < total) o_u[u] = v[j];
+            }
+        }
+    } else {
+        for (int j = 0; j < nr; ++j) {
+            const long long t = __shfl(slot, j, 64);
+            const U* sp = s_u + t * upr64;
+            U* dp = (U*)out + (row0 + j) * upr64;
+            for (int64_t k = lane; k < upr64; k += 64) dp[k] = sp[k];
+        }
+    }
+}
+
+// U0 < 0: the run-time field table; else CoopGather signatures (0: no field).
+template <int U0, int U1, int U2, int U3>
+__global__ __launch_bounds__(kBlock) void unpack_ranked_kernel(
+    RankedFields fp, int64_t n, const uint16_t* __restrict__ ids,
+    const uint16_t* __restrict__ ranks, const uint16_t* __restrict__ tile_starts, int nb,
+    const int64_t* __restrict__ offsets, int64_t T, int tile_rows,
+    const uint32_t* __restrict__ scan_err) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    long long* base = (long long*)smem;
+    if (scan_failed(scan_err)) return;
+    const int tid = threadIdx.x, w = tid >> 6, lane = lane_id();
+    const int64_t tile = xcd_tile(blockIdx.x, T);
+    for (int b = tid; b < nb; b += kBlock)
+        base[b] = offsets[(int64_t)b * T + tile] - (long long)tile_starts[tile * nb + b];
+    __syncthreads();
+    const int64_t trow0 = tile * (int64_t)tile_rows;
+    const int rows = (int)min((int64_t)tile_rows, n - trow0);
+    for (int r0 = 64 * w; r0 < rows; r0 += 64 * kWaves) {
+        const int nr = min(64, rows - r0);
+        const int64_t row0 = trow0 + r0;
+        long long slot = 0;
+        if (lane < nr) {
+            // ids >= nb: clamped as pack_ranked_kernel clamps them
+            const unsigned b = min((unsigned)ids[row0 + lane], (unsigned)(nb - 1));
+            const unsigned rk = ranks[row0 + lane];
+            // inside [0, n) for the arrays mgr_rank_ids + mgr_scan left; held
+            // there for any others, so that no read leaves the buffers
+            slot = min(max(base[b] + (long long)rk, 0ll), (long long)n - 1);
+        }
+        if constexpr (U0 >= 0) {
+            CoopGather<U0> f0;
+            CoopGather<U1> f1;
+            CoopGather<U2> f2;
+            CoopGather<U3> f3;
+            f0.load(fp.src[0], nullptr, slot, nr, lane);
+            f1.load(fp.src[1], nullptr, slot, nr, lane);
+            f2.load(fp.src[2], nullptr, slot, nr, lane);
+            f3.load(fp.src[3], nullptr, slot, nr, lane);
+            f0.store(fp.out[0], row0, nr, lane);
+            f1.store(fp.out[1], row0, nr, lane);
+            f2.store(fp.out[2], row0, nr, lane);
+            f3.store(fp.out[3], row0, nr, lane);
+        } else {
+            for (int f = 0; f < fp.nf; ++f) {
+                const uint8_t* __restrict__ src = fp.src[f];
+                uint8_t* __restrict__ out = fp.out[f];
+                const int64_t upr = fp.upr[f];
+                const uint32_t mg = fp.magic[f];
+                switch (fp.wlog[f]) {
+                    case 4: ranked_move<16>(src, out, upr, mg, slot, row0, nr, lane); break;
+                    case 3: ranked_move<8>(src, out, upr, mg, slot, row0, nr, lane); break;
+                    case 2: ranked_move<4>(src, out, upr, mg, slot, row0, nr, lane); break;
+                    case 1: ranked_move<2>(src, out, upr, mg, slot, row0, nr, lane); break;
+                    default: ranked_move<1>(src, out, upr, mg, slot, row0, nr, lane); break;
+                }
+            }
+        }
+    }
+}
+
+// mgr_unpack_ranked_fields: ONE launch for every field set.  Templated
+// signatures: one field of <= 16 units of 16/8/4 bytes, and the 2..4-field
+// sets of pack_coop_fields (config 5's four arrays first); every other set
+// takes the run-time table in the same launch -- nothing goes field by field.
+hipError_t launch_unpack_ranked_fields(int nf, const void* const* sorted, const int64_t* row_bytes,
+                                       int64_t n, const uint16_t* ids, const uint16_t* ranks,
+                                       const uint16_t* tile_starts, int nbins, int tile_rows,
+                                       const Workspace& ws, void* const* outs, hipStream_t s) {
+    if (n <= 0 || ws.T <= 0) return hipSuccess;
+    if (nf < 1 || nf > MGR_MAX_FIELDS || nbins < 1 || nbins > 1024 ||
+        (tile_rows != 2048 && tile_rows != 4096))
+        return hipErrorNotSupported;
+    RankedFields fp{};
+    fp.nf = nf;
+    int u[4] = {0, 0, 0, 0};
+    bool coop = nf <= 4;
+    for (int f = 0; f < nf; ++f) {
+        const int64_t rb = row_bytes[f];
+        const int wl = unit_log((uintptr_t)sorted[f] | (uintptr_t)outs[f] | (uintptr_t)rb);
+        fp.src[f] = (const uint8_t*)sorted[f];
+        fp.out[f] = (uint8_t*)outs[f];
+        fp.wlog[f] = (uint8_t)wl;
+        fp.upr[f] = rb >> wl;
+        fp.magic[f] = fp.upr[f] <= 64 ? (uint32_t)(((1u << 20) + fp.upr[f] - 1) / fp.upr[f]) : 0u;
+        if (coop) {
+            u[f] = coop_unit(sorted[f], rb, outs[f], nullptr);
+            coop = u[f] >= 0;
+        }
+    }
+    const int lds = align16(nbins * 8);
+    prof_begin(s, K_UNPACK_RANKED);
+    hipError_t e = hipErrorNotSupported;
+#define MGR_URK(A, B, C, D)                                                                     \
+    {                                                                                           \
+        hipLaunchKernelGGL((unpack_ranked_kernel<A, B, C, D>), dim3((unsigned)ws.T),            \
+                           dim3(kBlock), (size_t)lds, s, fp, n, ids, ranks, tile_starts, nbins, \
+                           ws.offsets, ws.T, tile_rows, ws.scan_err);                           \
+        e = hipGetLastError();                                                                  \
+    }
+    if (coop && hooks().unpack_kernel != 1) {
+        auto sig = [&](int a, int b, int c, int d) { return u[0] == a && u[1] == b && u[2] == c && u[3] == d; };
+        constexpr int F4x1 = 4 * 32 + 1, F4x3 = 4 * 32 + 3, F8x1 = 8 * 32 + 1, F8x3 = 8 * 32 + 3,
+                      F16x2 = 16 * 32 + 2, F4x9 = 4 * 32 + 9, F16x1 = 16 * 32 + 1, F8x2 = 8 * 32 + 2;
+        if (nf == 1) {
+#define MGR_UR1(W_, N_) case W_ * 32 + N_: MGR_URK(W_ * 32 + N_, 0, 0, 0) break;
+            switch (u[0]) {
+                MGR_UR1(16, 1) MGR_UR1(16, 2) MGR_UR1(16, 3) MGR_UR1(16, 4)
+                MGR_UR1(8, 1) MGR_UR1(8, 2) MGR_UR1(8, 3) MGR_UR1(8, 4)
+                MGR_UR1(8, 5) MGR_UR1(8, 6) MGR_UR1(8, 7) MGR_UR1(8, 8)
+                MGR_UR1(4, 1) MGR_UR1(4, 2) MGR_UR1(4, 3) MGR_UR1(4, 4)
+                MGR_UR1(4, 5) MGR_UR1(4, 6) MGR_UR1(4, 7) MGR_UR1(4, 8)
+                MGR_UR1(4, 9) MGR_UR1(4, 10) MGR_UR1(4, 11) MGR_UR1(4, 12)
+                MGR_UR1(4, 13) MGR_UR1(4, 14) MGR_UR1(4, 15) MGR_UR1(4, 16)
+                default: break;
+            }
+#undef MGR_UR1
+        }
+        else if (sig(F4x3, F4x3, F4x1, F8x1)) MGR_URK(F4x3, F4x3, F4x1, F8x1)
+        else if (sig(F8x3, F8x1, 0, 0)) MGR_URK(F8x3, F8x1, 0, 0)
+        else if (sig(F16x2, F8x3, 0, 0)) MGR_URK(F16x2, F8x3, 0, 0)
+        else if (sig(F4x9, F4x3, 0, 0)) MGR_URK(F4x9, F4x3, 0, 0)
+        else if (sig(F4x3, F8x1, 0, 0)) MGR_URK(F4x3, F8x1, 0, 0)
+        else if (sig(F16x1, F8x1, 0, 0)) MGR_URK(F16x1, F8x1, 0, 0)
+        else if (sig(F8x3, F8x3, F8x1, 0)) MGR_URK(F8x3, F8x3, F8x1, 0)
+        else if (sig(F4x3, F4x3, F8x1, 0)) MGR_URK(F4x3, F4x3, F8x1, 0)
+        else if (sig(F8x2, F8x1, 0, 0)) MGR_URK(F8x2, F8x1, 0, 0)
+    }
+    if (e == hipErrorNotSupported) MGR_URK(-1, 0, 0, 0)
+#undef MGR_URK
+    prof_end(s, K_UNPACK_RANKED);
+    return e;
+}
+
 }  // namespace mgr

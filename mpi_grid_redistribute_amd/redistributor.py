@@ -106,12 +106,70 @@ def _as_ids(fine_ids, n, dev, nbins):
     return t
 
 
-def _sort_by_ids(fields, ids, n, nb, dev, scratch=None, check_ids=True):
+class SortRoute:
+    """What ``unsort`` / ``return_to_source(..., sort_route=)`` need to bring
+    per-row results out of fine-cell order (``fine_cell_sort(...,
+    return_route=True)``): for the ranked sort (<= 1024 fine cells, sorted
+    fields of 4-byte multiples <= 64 B) the rows' ids, their ranks, the tiles'
+    cell starts and the workspace as mgr_rank_ids + mgr_scan left them -- the
+    inverse is one mgr_unpack_ranked_fields launch; for the other sorts the
+    destination bytes and workspace of mgr_count_ids + mgr_scan -- the inverse
+    is mgr_unpack_fields (bin = id, no drop bin, no redirect).  Buffers that
+    came from a Scratch are TAKEN OUT of it (the next call allocates anew),
+    fresh ones are kept; ids the caller's device tensor would alias are copied
+    (2 B/row), so later calls and the caller's writes leave a live route
+    alone, and it may be used any number of times.  Memory per live route,
+    ranked: about 4 B/row (ids + ranks) + 2 * T * nbins (T = ceil(n /
+    tile_rows)) + mgr_workspace_bytes(n, nbins, tile_rows); else 1-2 B/row +
+    the workspace.  Freed by ``release()``."""
+
+    def __init__(self, n, nbins, tile_rows, ws, ids=None, ranks=None, tile_starts=None, dest=None):
+        self.n, self.nbins, self.tile_rows = int(n), int(nbins), int(tile_rows)
+        self.ranked = dest is None
+        self._ws, self._ids, self._ranks, self._tstarts, self._dest = (ws, ids, ranks,
+                                                                        tile_starts, dest)
+
+    @property
+    def released(self):
+        return self._ws is None
+
+    def release(self):
+        """Free the route's device memory; it cannot be used afterwards."""
+        self._ws = self._ids = self._ranks = self._tstarts = self._dest = None
+
+
+def _unsort_into(sroute, srcs, rbs, outs):
+    """outs[f][r] = srcs[f][slot(r)] for the sort that made ``sroute``: flat
+    device tensors of sroute.n rows of rbs[f] bytes; one launch."""
+    n, s = sroute.n, _lib.stream_handle()
+    if n == 0:
+        return
+    if sroute.ranked:
+        _lib.call("mgr_unpack_ranked_fields", len(rbs), _ptrs([t.data_ptr() for t in srcs]),
+                  _i64s(rbs), n, _lib.ptr(sroute._ids), _lib.ptr(sroute._ranks),
+                  _lib.ptr(sroute._tstarts), sroute.nbins, sroute.tile_rows,
+                  _lib.ptr(sroute._ws), _ptrs([t.data_ptr() for t in outs]), s)
+    else:
+        _lib.call("mgr_unpack_fields", len(rbs), _ptrs([t.data_ptr() for t in srcs]), _i64s(rbs),
+                  n, _lib.ptr(sroute._dest), sroute.nbins, -1, sroute.tile_rows,
+                  _lib.ptr(sroute._ws), _ptrs([t.data_ptr() for t in outs]), -1, None, 0, -1, s)
+
+
+def _check_sort_route(sort_route):
+    if not isinstance(sort_route, SortRoute):
+        raise TypeError("sort_route: a SortRoute of fine_cell_sort(..., return_route=True)")
+    if sort_route.released:
+        raise ValueError("the sort route was released")
+
+
+def _sort_by_ids(fields, ids, n, nb, dev, scratch=None, check_ids=True, route=False):
     """Stable sort of every field by the uint16 ids (the fine cells): rank
     (mgr_rank_ids) or count (mgr_count_ids) -> scan -> pack.  Returns ([sorted
     flat fields], counts).  ``check_ids``: ids from the caller (not from this
     library's binning) -- an id >= nb is clamped by the kernels and turns the
-    counts into -1 (the failed-scan convention: host results raise)."""
+    counts into -1 (the failed-scan convention: host results raise).
+    ``route``: ([sorted], counts, SortRoute) -- the sort's buffers leave the
+    scratch and ``ids`` is kept, so the caller passes ids it owns."""
     hint = max([f.row_bytes for f in fields] + [1])
     s = _lib.stream_handle()
     counts = torch.empty(nb, dtype=torch.int64, device=dev)
@@ -154,7 +212,16 @@ def _sort_by_ids(fields, ids, n, nb, dev, scratch=None, check_ids=True):
             outs.append(o)
     if bad is not None:
         counts.masked_fill_(bad.ne(0), -1)
-    return outs, counts
+    if not route:
+        return outs, counts
+    if scratch is not None:   # the route owns them: the next sort allocates anew
+        for name in ("ws_fine", "dest_fine", "ranks_fine", "tstarts_fine"):
+            scratch.take(name)
+    if ranked:
+        sroute = SortRoute(n, nb, tile_rows, ws, ids=ids, ranks=ranks, tile_starts=tstarts)
+    else:
+        sroute = SortRoute(n, nb, tile_rows, ws, dest=dest)
+    return outs, counts, sroute
 
 
 def _payload(data, dev):
@@ -249,12 +316,14 @@ def _offsets_like(data, counts, dev):
     return offsets.cpu() if isinstance(data, torch.Tensor) else offsets.cpu().numpy()
 
 
-def _fine_sort(plan, coarse, dim, dev, data, position, return_positions, fine_ids=None):
+def _fine_sort(plan, coarse, dim, dev, data, position, return_positions, fine_ids=None,
+               return_route=False):
     """The fine cells of the rows -- ``fine_ids`` as given (computed at the
     source), else one read of the positions (mgr_bin_count_fine against the
     coarse plan, periodic=0: no wrap, no write-back; the fine cell is the fine
     plan's binning by construction, mgr_device.h bin_coord) -- then the
-    stable sort by them (_sort_by_ids)."""
+    stable sort by them (_sort_by_ids).  ``return_route``: the SortRoute of
+    the sort is appended to the result."""
     rows, multi = _payload(data, dev)
     pos = Positions(position, dim, dev, data_rows=_alias_rows(position, rows))
     if pos.n != rows[0].n:
@@ -273,12 +342,20 @@ def _fine_sort(plan, coarse, dim, dev, data, position, return_positions, fine_id
         ids = ids[:n]
     else:
         ids = _as_ids(fine_ids, n, dev, nb)
-    outs, counts = _sort_by_ids(fields, ids, n, nb, dev, check_ids=check)
+        if (return_route and isinstance(fine_ids, torch.Tensor) and n
+                and ids.untyped_storage().data_ptr() == fine_ids.untyped_storage().data_ptr()):
+            ids = ids.clone()   # the caller's tensor: the route keeps its own copy
+    sroute = None
+    if return_route:
+        outs, counts, sroute = _sort_by_ids(fields, ids, n, nb, dev, check_ids=check, route=True)
+    else:
+        outs, counts = _sort_by_ids(fields, ids, n, nb, dev, check_ids=check)
     nd = len(rows)
     res = [_results(rows, outs[:nd], n, multi)]
     if prow:
         res.append(prow.wrap(outs[nd], n))
-    return tuple(res) + (_offsets_like(rows[0].obj, counts, dev),)
+    res.append(_offsets_like(rows[0].obj, counts, dev))
+    return tuple(res) + ((sroute,) if return_route else ())
 
 
 class _IdField:
@@ -537,12 +614,17 @@ class MPIGridRedistributor:
         SoA payload.  ``return_route``: (result, route) -- ``result`` is what
         the call returns otherwise, ``route`` a Route for ``return_to_source``
         (not with ``overload_lengths``: halo rows are copies, their return is
-        a reduction; not with ``fine_cells``: a second permutation)."""
+        a reduction; not with ``fine_cells`` in this one call: redistribute
+        with ``return_route=True``, then ``fine_cell_sort(...,
+        return_route=True)``, and give both routes to ``return_to_source(
+        values, route, sort_route=...)``)."""
         if return_route and (overload_lengths is not None or fine_cells is not None):
             raise NotImplementedError(
                 "return_route together with overload_lengths or fine_cells: halo rows are "
-                "copies (their return is a reduction onto the owners) and the fine-cell sort "
-                "adds a second permutation; neither has a return path")
+                "copies (their return is a reduction onto the owners); for fine_cells use the "
+                "two-call route -- redistribute_by_position(..., return_positions=True, "
+                "return_route=True), then fine_cell_sort(..., return_route=True), then "
+                "return_to_source(values, route, sort_route=...)")
         fields, multi = _payload(data, self._dev)
         for d in (data if multi else [data]):
             self._check_host_alias(d, position)
@@ -594,7 +676,28 @@ class MPIGridRedistributor:
         ws, dest = self._scratch.take("ws"), self._scratch.take("dest")
         return Route(self, dest, ws, tile_rows, nb, drop_bin, n, self._last_layout)
 
-    def return_to_source(self, values, route):
+    def unsort(self, values, sort_route):
+        """The inverse of the ``fine_cell_sort`` that made ``sort_route``
+        (``return_route=True``): ``values`` -- one array, or a tuple / list of
+        up to MAX_FIELDS arrays, of ``sort_route.n`` rows each, of any dtype
+        and trailing shape, in sorted order (forces, densities, tags computed
+        per sorted row) -- come back in the order the rows had before the
+        sort: row i is the value of the row that was row i.  Containers as
+        ``return_to_source``.  One launch for all fields
+        (mgr_unpack_ranked_fields; mgr_unpack_fields for a sort that took the
+        non-ranked path); nothing is ranked or scanned again."""
+        _check_sort_route(sort_route)
+        fields, multi = _payload(values, self._dev)
+        n = sort_route.n
+        for i, f in enumerate(fields):
+            if f.n != n:
+                raise ValueError(f"values field {i} has {f.n} rows, the sort route has {n}")
+        rbs = [f.row_bytes for f in fields]
+        outs = [torch.empty(max(n * rb, 1), dtype=torch.uint8, device=self._dev) for rb in rbs]
+        _unsort_into(sort_route, [f.flat for f in fields], rbs, outs)
+        return _results(fields, outs, n, multi)
+
+    def return_to_source(self, values, route, sort_route=None):
         """The inverse of the redistribution that made ``route``: ``values``
         -- one array, or a tuple / list of up to MAX_FIELDS arrays, of
         ``route.n_local`` rows each, of any dtype and trailing shape (per-row
@@ -606,7 +709,11 @@ class MPIGridRedistributor:
         dropped is zero.  One reverse row exchange (exchange_back: the forward
         messages with sender and receiver swapped, no count exchange, no host
         sync) and one mgr_unpack_fields call; nothing is binned or scanned
-        again."""
+        again.  ``sort_route`` (a SortRoute of ``fine_cell_sort(...,
+        return_route=True)`` on the rows the route delivered): ``values`` are
+        in fine-cell order; they are unsorted straight into the buffers the
+        reverse exchange sends from (one mgr_unpack_ranked_fields launch, no
+        further copy)."""
         if not isinstance(route, Route):
             raise TypeError("route: a Route of redistribute_by_position(..., return_route=True)")
         if route.released:
@@ -617,6 +724,11 @@ class MPIGridRedistributor:
                               or not np.array_equal(o.box_length, self.box_length)):
             raise ValueError("the route was made by another redistributor (different size, "
                              "rank or plan)")
+        if sort_route is not None:
+            _check_sort_route(sort_route)
+            if sort_route.n != route.n_local:
+                raise ValueError(f"the sort route has {sort_route.n} rows, the route delivered "
+                                 f"{route.n_local}")
         fields, multi = _payload(values, self._dev)
         for i, f in enumerate(fields):
             if f.n != route.n_local:
@@ -625,6 +737,11 @@ class MPIGridRedistributor:
         self.comm.reset_traffic()
         n, stream = route.n_source, _lib.stream_handle()
         rbs = [f.row_bytes for f in fields]
+        flats = [f.flat for f in fields]
+        if sort_route is not None:   # out of fine-cell order, into the send buffers
+            flats = [self._scratch.get(f"unsort{i}", route.n_local * rb)
+                     for i, rb in enumerate(rbs)]
+            _unsort_into(sort_route, [f.flat for f in fields], rbs, flats)
 
         def unpack_all(stagings, vals, redirect_bin, offs):
             outs = [torch.empty(max(n * rb, 1), dtype=torch.uint8, device=self._dev)
@@ -637,7 +754,7 @@ class MPIGridRedistributor:
                       redirect_bin, _ptrs(reds) if redirect_bin >= 0 else None, 0, -1, stream)
             return outs
 
-        outs = exchange_back(self.comm, rbs, route.layout, [f.flat for f in fields], self.rank,
+        outs = exchange_back(self.comm, rbs, route.layout, flats, self.rank,
                              self._dev, unpack_all, scratch=self._scratch.get)
         return _results(fields, outs, n, multi)
 
@@ -785,7 +902,8 @@ class MPIGridRedistributor:
         res = _results(fields, ov_d if multi else [ov_d], mo, multi)
         return (res, prow.wrap(ov_p, mo)) if return_positions else res
 
-    def fine_cell_sort(self, data, position, fine_cells, return_positions=False, fine_ids=None):
+    def fine_cell_sort(self, data, position, fine_cells, return_positions=False, fine_ids=None,
+                       return_route=False):
         """Destination-side stable sort of this rank's rows by fine cell, for
         particle-mesh deposition (the reference has
         no such step).  The fine cell of a row is the reference's binning
@@ -797,10 +915,15 @@ class MPIGridRedistributor:
         ``return_positions`` -- in the containers of the inputs.
         ``fine_ids``: the rows' fine cells as computed at the source
         (uint16, ``GridPartitioner.partition_device(..., fine_cells=...)`` /
-        mgr_bin_count_fine); the rows are then not binned again."""
+        mgr_bin_count_fine); the rows are then not binned again.
+        ``return_route``: a SortRoute is appended to the tuple, for ``unsort``
+        and ``return_to_source(..., sort_route=)``; it owns the sort's ids,
+        ranks, tile starts and workspace (SortRoute: about 4 B/row + 2 * T *
+        nbins + the workspace) until ``release()``.  Without it nothing more
+        is allocated, copied or launched than the sort itself."""
         plan = self._fine_plan(fine_cells)
         return _fine_sort(plan, self._plan, self.dim, self._dev, data, position,
-                          return_positions, fine_ids)
+                          return_positions, fine_ids, return_route)
 
     def get_cell_number_from_indexes_host(self, indexes, periodic=True):
         """redist.py:73-85 on the host (neighbour ranks of the halo exchange)."""
