@@ -1,7 +1,8 @@
 // Device-side building blocks shared by the kernel translation units
 // (mgr_bin.hip, mgr_pack.hip, mgr_kernels.hip): IEEE/x86-exact scalar math
-// of the reference's wrap and binning, wave primitives, one-pass scan words,
-// streaming load/store policies, XCD-aware tile order; plus launch helpers.
+// of the reference's wrap and binning, wave primitives, the packs' round
+// ranking and tagged slots, one-pass scan words, streaming load/store
+// policies, XCD-aware tile order; plus launch helpers.
 #pragma once
 
 #include "mgr_internal.h"
@@ -587,6 +588,46 @@ __device__ __forceinline__ int rank_in(unsigned long long peers) {
     return __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
 }
 
+// Rank one 64-row round for the cooperative kernels (<= 64 bins): match_bin
+// and, from the same nbits ballots, lane l's count of bin l in the round.
+// *peers: the valid lanes holding this lane's bin b (0 for an invalid lane),
+// so rank_in(*peers) is the row's stable rank among them.  Returns the
+// round's count of bin `lane` (for any lane, valid or not).
+__device__ __forceinline__ int round_rank(unsigned b, bool valid, int lane, int nbits,
+                                          unsigned long long* peers) {
+    unsigned long long pe = __ballot(valid), mine = pe;
+    for (int i = 0; i < nbits; ++i) {
+        const unsigned long long m = __ballot((b >> i) & 1u);
+        pe &= ((b >> i) & 1u) ? m : ~m;
+        mine &= ((lane >> i) & 1) ? m : ~m;
+    }
+    *peers = valid ? pe : 0ull;
+    return __popcll(mine);
+}
+
+// ------------------------------------------------------------ tagged slots
+// A row's place in a pack's output as one value that travels by shfl: the
+// output row, bit 62 set when the row's bin is the redirect bin (the row
+// lives in the redirect output, counted from its row 0: seg_start); < 0: the
+// row is not moved (dropped, or past the end).
+constexpr int kSlotRedirectBit = 62;
+constexpr long long kSlotRedirect = 1ll << kSlotRedirectBit, kSlotMask = kSlotRedirect - 1;
+
+__device__ __forceinline__ long long tag_slot(long long slot, int bin, int redirect_bin) {
+    return slot | (bin == redirect_bin ? kSlotRedirect : 0ll);
+}
+__device__ __forceinline__ long long slot_row(long long t) { return t & kSlotMask; }
+__device__ __forceinline__ bool slot_redirected(long long t) {   // t >= 0
+    return (t >> kSlotRedirectBit) != 0;
+}
+
+// The 2-byte side field (fine cell, halo flags) of a row to its tagged slot.
+__device__ __forceinline__ void store_side(uint16_t* __restrict__ id_dst,
+                                           uint16_t* __restrict__ id_red, long long tgt,
+                                           unsigned idv) {
+    if (tgt >= 0) (slot_redirected(tgt) ? id_red : id_dst)[slot_row(tgt)] = (uint16_t)idv;
+}
+
 // Block-wide exclusive scan of one int64 per thread (256 threads).
 __device__ __forceinline__ long long block_excl_scan(long long v, long long* total,
                                                      long long* s_w /* [kWaves] */) {
@@ -990,6 +1031,12 @@ __device__ __forceinline__ int64_t xcd_tile_c(int64_t bid, int64_t T, int C) {
     if (bid >= (T / g) * g) return bid;
     const int64_t within = bid % g;
     return bid - within + (within & 7) * C + (within >> 3);
+}
+
+// The tile of workgroup blockIdx.x in a launch over tiles [t0, t0 + tn):
+// xcd > 0: in XCD chunks of xcd tiles (kXcdPackChunk); 0: in launch order.
+__device__ __forceinline__ int64_t tile_index(int64_t t0, int64_t tn, int xcd) {
+    return t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
 }
 
 // Streaming accesses: NT selects the nontemporal (nt) cache policy for data

@@ -227,4 +227,20 @@ int set_hook(const char* key, int64_t value);   // mgr_test_hook
 constexpr int kXcdPackChunk = 16;   // packs: tiles dealt to the XCDs in chunks of 16
 constexpr int kImgRoundsPerWave = 2;  // image pack: 64-row rounds per wave
 
+// log2 of the widest copy unit (<= 16 bytes) that divides every address and
+// size or-ed into a.
+static inline int unit_log(uintptr_t a) {
+    return (a & 15) == 0 ? 4 : (a & 7) == 0 ? 3 : (a & 3) == 0 ? 2 : (a & 1) == 0 ? 1 : 0;
+}
+
+// A field's signature for the cooperative multi-field kernels (packs and
+// unpacks alike), W * 32 + UPR: the unit width W -- the widest of 16/8/4 bytes
+// dividing its row and every pointer -- and its UPR <= 16 units per row; -1:
+// not a field they take.  (red may be null.)
+static inline int coop_unit(const void* src, int64_t rb, const void* dst, const void* red) {
+    const int wl = unit_log((uintptr_t)src | (uintptr_t)dst | (uintptr_t)rb | (uintptr_t)red);
+    if (wl < 2 || (rb >> wl) > 16) return -1;
+    return (1 << wl) * 32 + (int)(rb >> wl);
+}
+
 }  // namespace mgr

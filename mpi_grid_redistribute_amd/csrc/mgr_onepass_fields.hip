@@ -182,14 +182,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(8))) vo
     int cq[RPW], cnt = 0;
 #pragma unroll
     for (int q = 0; q < RPW; ++q) {
-        unsigned long long p = __ballot(valid[q]), mine = p;
-        for (int i = 0; i < g.nbits; ++i) {
-            const unsigned long long m = __ballot((b[q] >> i) & 1u);
-            p &= ((b[q] >> i) & 1u) ? m : ~m;
-            mine &= ((lane >> i) & 1) ? m : ~m;
-        }
-        pe[q] = p;
-        cq[q] = __popcll(mine);
+        cq[q] = round_rank(b[q], valid[q], lane, g.nbits, &pe[q]);
         cnt += cq[q];
     }
     if (lane < nb) s_cnt[w * nb + lane] = cnt;

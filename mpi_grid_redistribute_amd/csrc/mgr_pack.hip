@@ -99,7 +99,7 @@ __global__ __launch_bounds__(1024) void pack_coop_kernel(
     using U = typename Unit<W>::T;
     __shared__ int s_cnt[kCoopMaxRounds][64];
     const int w = threadIdx.x >> 6, lane = lane_id();
-    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t tile = tile_index(t0, tn, xcd);
     // wave w moves rounds w*RPW .. w*RPW+RPW-1 of the tile
     const int64_t row0 = tile * (int64_t)tile_rows + 64 * RPW * w;
     // issue every load of the wave's rounds first
@@ -137,16 +137,7 @@ __global__ __launch_bounds__(1024) void pack_coop_kernel(
     int cnt[RPW];
 #pragma unroll
     for (int q = 0; q < RPW; ++q) {
-        const bool valid = lane < nr[q];
-        unsigned long long pe = __ballot(valid);
-        unsigned long long mine = pe;
-        for (int i = 0; i < nbits; ++i) {
-            const unsigned long long m = __ballot((b[q] >> i) & 1u);
-            pe &= ((b[q] >> i) & 1u) ? m : ~m;
-            mine &= ((lane >> i) & 1) ? m : ~m;
-        }
-        peers[q] = valid ? pe : 0ull;
-        cnt[q] = __popcll(mine);
+        cnt[q] = round_rank(b[q], lane < nr[q], lane, nbits, &peers[q]);
         s_cnt[w * RPW + q][lane] = cnt[q];
     }
     __syncthreads();
@@ -159,18 +150,17 @@ __global__ __launch_bounds__(1024) void pack_coop_kernel(
         const long long base = __shfl(tbase, (int)b[q], 64);
         long long tgt = -1;
         if (lane < nr[q] && (int)b[q] != drop_bin)
-            tgt = (base + rank_in(peers[q])) | ((int)b[q] == redirect_bin ? (1ll << 62) : 0ll);
+            tgt = tag_slot(base + rank_in(peers[q]), (int)b[q], redirect_bin);
         tbase += cnt[q];
-        if (id_src && tgt >= 0)
-            ((tgt >> 62) ? id_red : id_dst)[tgt & ((1ll << 62) - 1)] = (uint16_t)idv[q];
+        if (id_src) store_side(id_dst, id_red, tgt, idv[q]);
 #pragma unroll
         for (int k = 0; k < UPR; ++k) {
             const int u = 64 * k + lane;
             const int r = u / UPR, part = u - r * UPR;
             const long long t = __shfl(tgt, r, 64);
             if (u < nr[q] * UPR && t >= 0) {
-                U* o = (t >> 62) ? r_u : d_u;
-                o[(t & ((1ll << 62) - 1)) * UPR + part] = v[q][k];
+                U* o = slot_redirected(t) ? r_u : d_u;
+                o[slot_row(t) * UPR + part] = v[q][k];
             }
         }
     }
@@ -202,7 +192,7 @@ struct CoopField {
                 if (64 * k + lane < nr * UPR) v[k] = sp[64 * k + lane];
         }
     }
-    // tgt: this lane's row's slot (bit 62: the redirect output), < 0: not written
+    // tgt: this lane's row's tagged slot
     __device__ __forceinline__ void store(uint8_t* __restrict__ dst, uint8_t* __restrict__ red,
                                           long long tgt, int nr, int lane) const {
         if constexpr (U != 0) {
@@ -214,8 +204,8 @@ struct CoopField {
                 const int r = u / UPR, part = u - r * UPR;
                 const long long t = __shfl(tgt, r, 64);
                 if (u < nr * UPR && t >= 0) {
-                    T* o = (t >> 62) ? r_u : d_u;
-                    o[(t & ((1ll << 62) - 1)) * UPR + part] = v[k];
+                    T* o = slot_redirected(t) ? r_u : d_u;
+                    o[slot_row(t) * UPR + part] = v[k];
                 }
             }
         }
@@ -237,7 +227,7 @@ __global__ __launch_bounds__(1024) void pack_coop_fields_kernel(
     uint16_t* __restrict__ id_dst, uint16_t* __restrict__ id_red) {
     __shared__ int s_cnt[kCoopMaxRounds][64];
     const int w = threadIdx.x >> 6, lane = lane_id();
-    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t tile = tile_index(t0, tn, xcd);
     const int64_t row0 = tile * (int64_t)tile_rows + 64 * w;
     const int nr = (int)max((int64_t)0, min((int64_t)64, n - row0));
     // the destination bytes first, waited for, then every field's loads
@@ -256,22 +246,15 @@ __global__ __launch_bounds__(1024) void pack_coop_fields_kernel(
     f3.load(fp.src[3], row0, nr, lane);
     // rank inside the round; lane l counts bin l
     const bool valid = lane < nr;
-    unsigned long long pe = __ballot(valid), mine = pe;
-    for (int i = 0; i < nbits; ++i) {
-        const unsigned long long m = __ballot((b >> i) & 1u);
-        pe &= ((b >> i) & 1u) ? m : ~m;
-        mine &= ((lane >> i) & 1) ? m : ~m;
-    }
-    if (!valid) pe = 0ull;
-    s_cnt[w][lane] = __popcll(mine);
+    unsigned long long pe;
+    s_cnt[w][lane] = round_rank(b, valid, lane, nbits, &pe);
     __syncthreads();
     if (scan_failed(scan_err)) return;
     for (int j = 0; j < w; ++j) tbase += s_cnt[j][lane];
     const long long base = __shfl(tbase, (int)b, 64);
     long long tgt = -1;
-    if (valid && (int)b != drop_bin)
-        tgt = (base + rank_in(pe)) | ((int)b == redirect_bin ? (1ll << 62) : 0ll);
-    if (id_src && tgt >= 0) ((tgt >> 62) ? id_red : id_dst)[tgt & ((1ll << 62) - 1)] = (uint16_t)idv;
+    if (valid && (int)b != drop_bin) tgt = tag_slot(base + rank_in(pe), (int)b, redirect_bin);
+    if (id_src) store_side(id_dst, id_red, tgt, idv);
     f0.store(fp.dst[0], fp.red[0], tgt, nr, lane);
     f1.store(fp.dst[1], fp.red[1], tgt, nr, lane);
     f2.store(fp.dst[2], fp.red[2], tgt, nr, lane);
@@ -623,11 +606,6 @@ __global__ __launch_bounds__(256) void msel_pack_wide_kernel(
     }
 }
 
-// log2 of the widest copy unit (<= 16 bytes) that divides every address in a
-static inline int unit_log(uintptr_t a) {
-    return (a & 15) == 0 ? 4 : (a & 7) == 0 ? 3 : (a & 3) == 0 ? 2 : (a & 1) == 0 ? 1 : 0;
-}
-
 static hipError_t launch_msel_pack_wide(int nfields, const void* const* srcs,
                                         const int64_t* row_bytes, int64_t n,
                                         const uint16_t* flags, int nsets, const int* masks,
@@ -709,7 +687,7 @@ hipError_t launch_msel_pack(int nfields, const void* const* srcs, const int64_t*
                            : dsts[0 * nsets + k] ? (uint8_t*)dsts[f * nsets + k] : nullptr;
             a |= (uintptr_t)fs.dst[f][k];
         }
-        fs.wlog[f] = (a & 15) == 0 ? 4 : (a & 7) == 0 ? 3 : (a & 3) == 0 ? 2 : (a & 1) == 0 ? 1 : 0;
+        fs.wlog[f] = unit_log(a);
     }
     unsigned u = 0;
     for (int k = 0; k < nsets; ++k) u |= (unsigned)sb.m[k];
@@ -759,7 +737,7 @@ __global__ __launch_bounds__(1024) void pack_img_kernel(
     unsigned long long* gaddr = (unsigned long long*)(img + RBYTES);
     uint8_t* ibin = img + RBYTES + 64 * 8;
     uint32_t* imgw = (uint32_t*)img;
-    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t tile = tile_index(t0, tn, xcd);
     const int64_t row0 = tile * (int64_t)tile_rows + (int64_t)WR * w;
     const int nrows = (int)max((int64_t)0, min((int64_t)WR, n - row0));
     const int nbytes = nrows * RB;
@@ -818,14 +796,7 @@ __global__ __launch_bounds__(1024) void pack_img_kernel(
     int cq[RPW], cnt = 0;
 #pragma unroll
     for (int q = 0; q < RPW; ++q) {
-        unsigned long long p = __ballot(valid[q]), mine = p;
-        for (int i = 0; i < nbits; ++i) {
-            const unsigned long long m = __ballot((b[q] >> i) & 1u);
-            p &= ((b[q] >> i) & 1u) ? m : ~m;
-            mine &= ((lane >> i) & 1) ? m : ~m;
-        }
-        pe[q] = p;
-        cq[q] = __popcll(mine);
+        cq[q] = round_rank(b[q], valid[q], lane, nbits, &pe[q]);
         cnt += cq[q];
     }
     s_cnt[w * 64 + lane] = cnt;
@@ -910,6 +881,15 @@ struct PackFieldsArgs {
     int loff[kFieldsMax];        // byte offset of field f's rows in a wave's LDS area
     int nf;
     int wave_lds;                // LDS bytes per wave
+    // field nf: its rows of a wave at LDS offset loff; returns the next offset
+    int add(const void* s, void* d, void* r, int row_bytes, int off) {
+        src[nf] = (const uint8_t*)s;
+        dst[nf] = (uint8_t*)d;
+        red[nf] = (uint8_t*)r;
+        rb[nf] = row_bytes;
+        loff[nf++] = off;
+        return off + kFieldsWR * row_bytes;
+    }
 };
 // a wave's LDS after the fields' rows: per-bin output address (one field at
 // a time), per-bin image row offset, slot -> wave row, slot -> bin
@@ -969,7 +949,7 @@ __global__ __launch_bounds__(1024) void pack_fields_kernel(
     long long* rowoff = (long long*)(tail + 64 * 8);            // [64]
     uint8_t* inv = tail + 64 * 16;                              // slot -> wave row
     uint8_t* ibin = inv + WR;                                   // slot -> bin
-    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t tile = tile_index(t0, tn, xcd);
     const int64_t row0 = tile * (int64_t)tile_rows + (int64_t)WR * w;
     const int nrows = __builtin_amdgcn_readfirstlane((int)max((int64_t)0, min((int64_t)WR, n - row0)));
     unsigned braw[RPW], b[RPW], idv[RPW];
@@ -1009,14 +989,7 @@ __global__ __launch_bounds__(1024) void pack_fields_kernel(
     int cq[RPW], cnt = 0;
 #pragma unroll
     for (int q = 0; q < RPW; ++q) {
-        unsigned long long p = __ballot(valid[q]), mine = p;
-        for (int i = 0; i < nbits; ++i) {
-            const unsigned long long m = __ballot((b[q] >> i) & 1u);
-            p &= ((b[q] >> i) & 1u) ? m : ~m;
-            mine &= ((lane >> i) & 1) ? m : ~m;
-        }
-        pe[q] = p;
-        cq[q] = __popcll(mine);
+        cq[q] = round_rank(b[q], valid[q], lane, nbits, &pe[q]);
         cnt += cq[q];
     }
     s_cnt[w * 64 + lane] = cnt;
@@ -1127,7 +1100,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))) void 
     // the waves' bin counts [nw][64], after the staging (sized by the waves,
     // so six 512-row workgroups of config 5's SoA fields fit a CU's LDS)
     int (*s_cnt)[64] = (int (*)[64])(ibin + align16(tile_rows) + nw * fa.wave_lds);
-    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t tile = tile_index(t0, tn, xcd);
     const int64_t tile0 = tile * (int64_t)tile_rows;
     const int64_t row0 = tile0 + (int64_t)WR * w;
     const int nrows = __builtin_amdgcn_readfirstlane((int)max((int64_t)0, min((int64_t)WR, n - row0)));
@@ -1163,14 +1136,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))) void 
     int cq[RPW], cnt = 0;
 #pragma unroll
     for (int q = 0; q < RPW; ++q) {
-        unsigned long long p = __ballot(valid[q]), mine = p;
-        for (int i = 0; i < nbits; ++i) {
-            const unsigned long long m = __ballot((b[q] >> i) & 1u);
-            p &= ((b[q] >> i) & 1u) ? m : ~m;
-            mine &= ((lane >> i) & 1) ? m : ~m;
-        }
-        pe[q] = p;
-        cq[q] = __popcll(mine);
+        cq[q] = round_rank(b[q], valid[q], lane, nbits, &pe[q]);
         cnt += cq[q];
     }
     s_cnt[w][lane] = cnt;
@@ -1268,7 +1234,7 @@ __global__ __launch_bounds__(1024) void pack_many_kernel(
     long long* s_off = (long long*)smem;                       // [nb] running bin bases
     uint16_t* tab = (uint16_t*)(smem + align16(nb * 8));       // [R][nb]
     const int w = threadIdx.x >> 6, lane = lane_id();
-    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t tile = tile_index(t0, tn, xcd);
     if (scan_failed(scan_err)) return;
     for (int bb = threadIdx.x; bb < nb; bb += blockDim.x)
         s_off[bb] = seg_start(offsets, bin_starts, T, tile, bb, redirect_bin);
@@ -1322,16 +1288,16 @@ __global__ __launch_bounds__(1024) void pack_many_kernel(
         for (int q = 0; q < RPW; ++q) {
             long long tgt = -1;
             if (lane < nr[q] && (int)b[q] != drop_bin)
-                tgt = (s_off[b[q]] + tab[(w * RPW + q) * nb + b[q]] + rank_in(peers[q])) |
-                      ((int)b[q] == redirect_bin ? (1ll << 62) : 0ll);
+                tgt = tag_slot(s_off[b[q]] + tab[(w * RPW + q) * nb + b[q]] + rank_in(peers[q]),
+                               (int)b[q], redirect_bin);
 #pragma unroll
             for (int k = 0; k < UPR; ++k) {
                 const int u = 64 * k + lane;
                 const int r = u / UPR, part = u - r * UPR;
                 const long long t = __shfl(tgt, r, 64);
                 if (u < nr[q] * UPR && t >= 0) {
-                    U* o = (t >> 62) ? r_u : d_u;
-                    o[(t & ((1ll << 62) - 1)) * UPR + part] = v[q][k];
+                    U* o = slot_redirected(t) ? r_u : d_u;
+                    o[slot_row(t) * UPR + part] = v[q][k];
                 }
             }
         }
@@ -1378,6 +1344,50 @@ struct SideField {
     bool used = false;
 };
 
+// One pack as the launchers hand it down: launch_pack's arguments (nb =
+// nbins), the side field and the launch's snapshot of the test hooks.  Built
+// once in launch_pack_rows; a multi-field pack (launch_pack_fields) fills the
+// tile context only -- its arrays travel in the kernels' own tables.
+struct PackJob {
+    const void* src;
+    int64_t row_bytes, n;
+    const void* dest;
+    int nb, drop_bin, tile_rows;
+    const Workspace& ws;
+    void* dst;
+    int redirect_bin;
+    void* redirect_dst;
+    hipStream_t s;
+    SideField* side;
+    const Hooks& h;
+};
+
+// fn(std::integral_constant<int, UPR>) for upr = the row's units of W bytes,
+// UPR at compile time: rows of <= 64 bytes in 16/8/4-byte units (1..4, 1..8,
+// 1..16 units: registers, no scratch); hipErrorNotSupported for other shapes.
+template <int W, typename Fn>
+static hipError_t dispatch_upr(int64_t upr, Fn fn) {
+#define MGR_UPR(U_) case U_: return fn(std::integral_constant<int, U_>{});
+    switch ((int)upr) {
+        MGR_UPR(1) MGR_UPR(2) MGR_UPR(3) MGR_UPR(4)
+        default: break;
+    }
+    if constexpr (W <= 8) {
+        switch ((int)upr) {
+            MGR_UPR(5) MGR_UPR(6) MGR_UPR(7) MGR_UPR(8)
+            default: break;
+        }
+    }
+    if constexpr (W == 4) {
+        switch ((int)upr) {
+            MGR_UPR(9) MGR_UPR(10) MGR_UPR(11) MGR_UPR(12) MGR_UPR(13) MGR_UPR(14) MGR_UPR(15) MGR_UPR(16)
+            default: break;
+        }
+    }
+#undef MGR_UPR
+    return hipErrorNotSupported;
+}
+
 // pack_many_kernel: one super-round of 64 * R rows per tile (the uint16
 // [R][nbins] LDS table stays <= 128 KiB at 4096 rows and 1024 bins; A/B: 2-16
 // super-rounds per tile, i.e. longer per-bin runs, measured slower).
@@ -1411,148 +1421,91 @@ int pack_tile_rows(int64_t row_bytes, int nbins) {
 }
 
 template <int W, typename DestT, bool kWide>
-static hipError_t pack_t(const void* src, int64_t row_bytes, int64_t n, const void* dest, int nb,
-                         int drop_bin, int tile_rows, const Workspace& ws, void* dst,
-                         int redirect_bin, void* redirect_dst, hipStream_t s) {
+static hipError_t pack_t(const PackJob& j) {
     auto k = pack_kernel<W, DestT, kWide>;
-    const int per_wave = align16(nb * 8) + align16(nb * 4);
+    const Workspace& ws = j.ws;
+    const int per_wave = align16(j.nb * 8) + align16(j.nb * 4);
     const int wpb = waves_per_block(per_wave);
     const int lds = per_wave * wpb;
     ensure_lds(k, lds);
     const int64_t grid = (ws.tn + wpb - 1) / wpb;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * wpb), (size_t)lds, s,
-                       (const uint8_t*)src, row_bytes / W, n, (const DestT*)dest, nb,
-                       nbits_for(nb), drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn,
-                       tile_rows,
-                       per_wave, (uint8_t*)dst, redirect_bin, (uint8_t*)redirect_dst, ws.scan_err);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * wpb), (size_t)lds, j.s,
+                       (const uint8_t*)j.src, j.row_bytes / W, j.n, (const DestT*)j.dest, j.nb,
+                       nbits_for(j.nb), j.drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn,
+                       j.tile_rows, per_wave, (uint8_t*)j.dst, j.redirect_bin,
+                       (uint8_t*)j.redirect_dst, ws.scan_err);
     return hipGetLastError();
+}
+
+template <int W, int UPR, int RPW>
+static void launch_pack_coop(const PackJob& j, int threads) {
+    const Workspace& ws = j.ws;
+    // selection packs (2 bins, one dropped: the halo's rows to send) skip
+    // the loads of dropped rows; elsewhere loads go out before the bins are known
+    const int sel = j.nb <= 2 && j.drop_bin >= 0;
+    const SideField* side = j.side;
+    hipLaunchKernelGGL((pack_coop_kernel<W, UPR, RPW>), dim3((unsigned)ws.tn), dim3(threads), 0,
+                       j.s, (const uint8_t*)j.src, j.n, (const uint8_t*)j.dest, j.nb,
+                       nbits_for(j.nb), j.drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn,
+                       j.tile_rows, (uint8_t*)j.dst, j.redirect_bin, (uint8_t*)j.redirect_dst,
+                       kXcdPackChunk, sel, ws.scan_err, side ? side->src : nullptr,
+                       side ? side->dst : nullptr, side ? side->red : nullptr);
 }
 
 template <int W, int UPR>
-static hipError_t pack_coop_u(const void* src, int64_t n, const void* dest, int nb, int drop_bin,
-                              int tile_rows, const Workspace& ws, void* dst, int redirect_bin,
-                              void* redirect_dst, hipStream_t s, SideField* side, const Hooks& h) {
-    if (h.pack_generic || tile_rows > 2048) return hipErrorNotSupported;
+static hipError_t pack_coop_u(const PackJob& j) {
+    if (j.h.pack_generic || j.tile_rows > 2048) return hipErrorNotSupported;
     // one wave per RPW 64-row rounds of the tile (<= 16 waves)
-    const int rpw = tile_rows > 1024 ? 2 : 1;
-    const int threads = tile_rows / rpw;
-#define MGR_PCK(RPW_)                                                                         \
-    hipLaunchKernelGGL((pack_coop_kernel<W, UPR, RPW_>), dim3((unsigned)ws.tn), dim3(threads), 0, \
-                       s, (const uint8_t*)src, n, (const uint8_t*)dest, nb, nbits_for(nb),     \
-                       drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn, tile_rows,     \
-                       (uint8_t*)dst,                                                          \
-                       redirect_bin, (uint8_t*)redirect_dst, kXcdPackChunk, sel, ws.scan_err, \
-                       side ? side->src : nullptr, side ? side->dst : nullptr,         \
-                       side ? side->red : nullptr)
-    // selection packs (2 bins, one dropped: the halo's rows to send) skip
-    // the loads of dropped rows; elsewhere loads go out before the bins are known
-    const int sel = nb <= 2 && drop_bin >= 0;
-    if (side) side->used = side->src != nullptr;
-    if (rpw == 2) MGR_PCK(2); else MGR_PCK(1);
-#undef MGR_PCK
+    const int rpw = j.tile_rows > 1024 ? 2 : 1;
+    if (j.side) j.side->used = j.side->src != nullptr;
+    if (rpw == 2) launch_pack_coop<W, UPR, 2>(j, j.tile_rows / 2);
+    else launch_pack_coop<W, UPR, 1>(j, j.tile_rows);
     return hipGetLastError();
 }
 
-// Compile-time units per row for rows of <= 64 bytes in 16/8/4-byte units
-// (registers, no scratch); returns hipErrorNotSupported for other shapes.
-template <int W>
-static hipError_t pack_coop_t(const void* src, int64_t row_bytes, int64_t n, const void* dest,
-                               int nb, int drop_bin, int tile_rows, const Workspace& ws,
-                               void* dst, int redirect_bin, void* redirect_dst, hipStream_t s,
-                               SideField* side, const Hooks& h) {
-#define MGR_PS(U_) case U_: return pack_coop_u<W, U_>(src, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s, side, h);
-    if constexpr (W >= 4) {
-        switch ((int)(row_bytes / W)) {
-            MGR_PS(1) MGR_PS(2) MGR_PS(3) MGR_PS(4)
-            default: break;
-        }
-        if constexpr (W <= 8) {
-            switch ((int)(row_bytes / W)) {
-                MGR_PS(5) MGR_PS(6) MGR_PS(7) MGR_PS(8)
-                default: break;
-            }
-        }
-        if constexpr (W == 4) {
-            switch ((int)(row_bytes / W)) {
-                MGR_PS(9) MGR_PS(10) MGR_PS(11) MGR_PS(12) MGR_PS(13) MGR_PS(14) MGR_PS(15) MGR_PS(16)
-                default: break;
-            }
-        }
-    }
-#undef MGR_PS
-    return hipErrorNotSupported;
+template <int W, int UPR, typename DestT, int RPW>
+static void launch_pack_many(const PackJob& j, int lds) {
+    auto k = pack_many_kernel<W, UPR, DestT, RPW>;
+    const Workspace& ws = j.ws;
+    ensure_lds(k, lds);
+    hipLaunchKernelGGL(k, dim3((unsigned)ws.tn), dim3(1024), (size_t)lds, j.s,
+                       (const uint8_t*)j.src, j.n, (const DestT*)j.dest, j.nb, nbits_for(j.nb),
+                       j.drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn, j.tile_rows,
+                       (uint8_t*)j.dst, j.redirect_bin, (uint8_t*)j.redirect_dst, kXcdPackChunk,
+                       ws.scan_err);
 }
 
 template <int W, int UPR, typename DestT>
-static hipError_t pack_many_u(const void* src, int64_t n, const void* dest, int nb, int drop_bin,
-                              int tile_rows, const Workspace& ws, void* dst, int redirect_bin,
-                              void* redirect_dst, hipStream_t s) {
-    const int round_rows = many_round_rows(nb);
-    if (tile_rows % round_rows) return hipErrorNotSupported;
-    const int lds = align16(nb * 8) + (round_rows / 64) * nb * 2;
-#define MGR_PMK(RPW_)                                                                          \
-    {                                                                                          \
-        auto k = pack_many_kernel<W, UPR, DestT, RPW_>;                                        \
-        ensure_lds(k, lds);                                                                    \
-        hipLaunchKernelGGL(k, dim3((unsigned)ws.tn), dim3(1024), (size_t)lds, s,               \
-                           (const uint8_t*)src, n, (const DestT*)dest, nb, nbits_for(nb),      \
-                           drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn, tile_rows, \
-                           (uint8_t*)dst,                                                      \
-                           redirect_bin, (uint8_t*)redirect_dst, kXcdPackChunk, ws.scan_err); \
-    }
-    if (round_rows == 4096) MGR_PMK(4)
-    else if (round_rows == 2048) MGR_PMK(2)
+static hipError_t pack_many_u(const PackJob& j) {
+    const int round_rows = many_round_rows(j.nb);
+    if (j.tile_rows % round_rows) return hipErrorNotSupported;
+    const int lds = align16(j.nb * 8) + (round_rows / 64) * j.nb * 2;
+    if (round_rows == 4096) launch_pack_many<W, UPR, DestT, 4>(j, lds);
+    else if (round_rows == 2048) launch_pack_many<W, UPR, DestT, 2>(j, lds);
     else return hipErrorNotSupported;
-#undef MGR_PMK
     return hipGetLastError();
 }
 
-template <int W, typename DestT>
-static hipError_t pack_many_t(const void* src, int64_t row_bytes, int64_t n, const void* dest,
-                              int nb, int drop_bin, int tile_rows, const Workspace& ws, void* dst,
-                              int redirect_bin, void* redirect_dst, hipStream_t s) {
-#define MGR_PM(U_) case U_: return pack_many_u<W, U_, DestT>(src, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s);
-    switch ((int)(row_bytes / W)) {
-        MGR_PM(1) MGR_PM(2) MGR_PM(3) MGR_PM(4)
-        default: break;
-    }
-    if constexpr (W <= 8) {
-        switch ((int)(row_bytes / W)) {
-            MGR_PM(5) MGR_PM(6) MGR_PM(7) MGR_PM(8)
-            default: break;
-        }
-    }
-    if constexpr (W == 4) {
-        switch ((int)(row_bytes / W)) {
-            MGR_PM(9) MGR_PM(10) MGR_PM(11) MGR_PM(12) MGR_PM(13) MGR_PM(14) MGR_PM(15) MGR_PM(16)
-            default: break;
-        }
-    }
-#undef MGR_PM
-    return hipErrorNotSupported;
-}
-
 template <int RB>
-static hipError_t pack_img_t(const void* src, int64_t n, const void* dest, int nb, int drop_bin,
-                             int tile_rows, const Workspace& ws, void* dst, int redirect_bin,
-                             void* redirect_dst, hipStream_t s, SideField* side) {
+static hipError_t pack_img_t(const PackJob& j) {
     // two 64-row rounds per wave (A/B, 36-B records: 0.90-0.92 vs 1.02-1.05
     // ms per 64M with one, 4: 1.17 -- a wave's fixed per-round chain of load,
     // count exchange, LDS permutation and store then moves twice the rows);
     // tiles that are not a multiple of two rounds go to the coop pack
     constexpr int rpw = kImgRoundsPerWave;
-    if (tile_rows % (64 * rpw)) return hipErrorNotSupported;
-    const int nw = tile_rows / (64 * rpw);
+    if (j.tile_rows % (64 * rpw)) return hipErrorNotSupported;
+    const Workspace& ws = j.ws;
+    SideField* side = j.side;
+    const int nw = j.tile_rows / (64 * rpw);
     const int lds = nw * 64 * 4 + nw * (64 * rpw * RB + 64 * 8 + 64 * rpw);
-    const bool sel = nb <= 2 && drop_bin >= 0;
+    const bool sel = j.nb <= 2 && j.drop_bin >= 0;
     auto k = sel ? pack_img_kernel<RB, rpw, true> : pack_img_kernel<RB, rpw, false>;
     ensure_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)ws.tn), dim3(64 * nw), (size_t)lds, s,
-                       (const uint8_t*)src, n, (const uint8_t*)dest, nb, nbits_for(nb), drop_bin,
-                       ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn, tile_rows, (uint8_t*)dst,
-                       redirect_bin,
-                       (uint8_t*)redirect_dst, kXcdPackChunk, ws.scan_err,
-                       side ? side->src : nullptr, side ? side->dst : nullptr,
+    hipLaunchKernelGGL(k, dim3((unsigned)ws.tn), dim3(64 * nw), (size_t)lds, j.s,
+                       (const uint8_t*)j.src, j.n, (const uint8_t*)j.dest, j.nb, nbits_for(j.nb),
+                       j.drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn, j.tile_rows,
+                       (uint8_t*)j.dst, j.redirect_bin, (uint8_t*)j.redirect_dst, kXcdPackChunk,
+                       ws.scan_err, side ? side->src : nullptr, side ? side->dst : nullptr,
                        side ? side->red : nullptr);
     if (side) side->used = side->src != nullptr;
     return hipGetLastError();
@@ -1748,22 +1701,18 @@ hipError_t launch_pack_ranked(const void* src, int64_t row_bytes, int64_t n, con
 // Rows of 24..60 (pack_img 2: 12..60) bytes, 4-byte multiples but not 16-byte ones: the
 // image pack (16-byte global accesses) when the source is 16-byte aligned,
 // the outputs 4-byte aligned, <= 64 bins and <= 16 waves per tile.
-static hipError_t pack_img(const void* src, int64_t row_bytes, int64_t n, const void* dest,
-                           int nb, int drop_bin, int tile_rows, const Workspace& ws, void* dst,
-                           int redirect_bin, void* redirect_dst, hipStream_t s, SideField* side,
-                           const Hooks& h) {
-    uintptr_t a = (uintptr_t)dst | (uintptr_t)row_bytes;
-    if (redirect_dst) a |= (uintptr_t)redirect_dst;
+static hipError_t pack_img(const PackJob& j) {
+    uintptr_t a = (uintptr_t)j.dst | (uintptr_t)j.row_bytes | (uintptr_t)j.redirect_dst;
     // pack_img 1: rows of >= 24 bytes (A/B: 36 B 0.90 vs 1.05 ms, 40 B 0.97 vs
     // 1.00, 24 B 0.70 vs 0.71; 12 B 0.56 vs 0.48 -- the LDS passes cost more
     // than narrow units for small rows); 2: every size it takes (tests)
-    const int64_t min_rb = h.pack_img_all ? 12 : 24;
-    if (((uintptr_t)src & 15) || (a & 3) || row_bytes % 16 == 0 ||
-        row_bytes < min_rb || row_bytes > 60 || nb > 64 || tile_rows > 1024 ||
-        dest_bytes(nb) != 1)
+    const int64_t min_rb = j.h.pack_img_all ? 12 : 24;
+    if (((uintptr_t)j.src & 15) || (a & 3) || j.row_bytes % 16 == 0 ||
+        j.row_bytes < min_rb || j.row_bytes > 60 || j.nb > 64 || j.tile_rows > 1024 ||
+        dest_bytes(j.nb) != 1)
         return hipErrorNotSupported;
-#define MGR_PI(RB_) case RB_: return pack_img_t<RB_>(src, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s, side);
-    switch ((int)row_bytes) {
+#define MGR_PI(RB_) case RB_: return pack_img_t<RB_>(j);
+    switch ((int)j.row_bytes) {
         MGR_PI(12) MGR_PI(20) MGR_PI(24) MGR_PI(28) MGR_PI(36) MGR_PI(40) MGR_PI(44)
         MGR_PI(52) MGR_PI(56) MGR_PI(60)
         default: break;
@@ -1772,37 +1721,35 @@ static hipError_t pack_img(const void* src, int64_t row_bytes, int64_t n, const 
     return hipErrorNotSupported;
 }
 
+// The pack of one array in W-byte units: the many-bin, cooperative or
+// wave-per-tile kernel its shape takes.
 template <int W>
-static hipError_t pack_w(const void* src, int64_t row_bytes, int64_t n, const void* dest, int nb,
-                         int drop_bin, int tile_rows, const Workspace& ws, void* dst,
-                         int redirect_bin, void* redirect_dst, hipStream_t s, SideField* side,
-                         const Hooks& h) {
+static hipError_t pack_w(const PackJob& j) {
+    const bool dest8 = dest_bytes(j.nb) == 1;
     if constexpr (W >= 4) {
-        if (nb > 64 && nb <= 1024 && row_bytes <= 64 && tile_rows == many_round_rows(nb)) {
-            const hipError_t e = dest_bytes(nb) == 1
-                ? pack_many_t<W, uint8_t>(src, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s)
-                : pack_many_t<W, uint16_t>(src, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s);
+        const int64_t upr = j.row_bytes / W;
+        if (j.nb > 64 && j.nb <= 1024 && j.row_bytes <= 64 && j.tile_rows == many_round_rows(j.nb)) {
+            const hipError_t e = dispatch_upr<W>(upr, [&](auto u) {
+                return dest8 ? pack_many_u<W, u(), uint8_t>(j) : pack_many_u<W, u(), uint16_t>(j);
+            });
+            if (e != hipErrorNotSupported) return e;
+        }
+        if (j.nb <= 64 && j.row_bytes <= 64) {
+            const hipError_t e = dispatch_upr<W>(upr, [&](auto u) { return pack_coop_u<W, u()>(j); });
             if (e != hipErrorNotSupported) return e;
         }
     }
     if constexpr (W == 2) {   // 2-byte rows (the fine cells travelling with config-5 rows)
-        if (nb <= 64 && row_bytes == 2) {
-            const hipError_t e = pack_coop_u<2, 1>(src, n, dest, nb, drop_bin, tile_rows, ws, dst,
-                                                   redirect_bin, redirect_dst, s, nullptr, h);
+        if (j.nb <= 64 && j.row_bytes == 2) {
+            PackJob plain = j;   // the side field is left to its own pack
+            plain.side = nullptr;
+            const hipError_t e = pack_coop_u<2, 1>(plain);
             if (e != hipErrorNotSupported) return e;
         }
     }
-    if (nb <= 64 && row_bytes <= 64 && W >= 4) {
-        const hipError_t e = pack_coop_t<W>(src, row_bytes, n, dest, nb, drop_bin, tile_rows,
-                                             ws, dst, redirect_bin, redirect_dst, s, side, h);
-        if (e != hipErrorNotSupported) return e;
-    }
-    const bool wide = row_bytes > 256;
-    if (dest_bytes(nb) == 1)
-        return wide ? pack_t<W, uint8_t, true>(src, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s)
-                    : pack_t<W, uint8_t, false>(src, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s);
-    return wide ? pack_t<W, uint16_t, true>(src, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s)
-                : pack_t<W, uint16_t, false>(src, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s);
+    const bool wide = j.row_bytes > 256;
+    if (dest8) return wide ? pack_t<W, uint8_t, true>(j) : pack_t<W, uint8_t, false>(j);
+    return wide ? pack_t<W, uint16_t, true>(j) : pack_t<W, uint16_t, false>(j);
 }
 
 static hipError_t launch_pack_rows(const void* src, int64_t row_bytes, int64_t n,
@@ -1825,22 +1772,25 @@ hipError_t launch_pack(const void* src, int64_t row_bytes, int64_t n, const void
                             redirect_bin, ids_red, s, nullptr);
 }
 
-// The cooperative multi-field kernel for a field signature it is built for
-// (hipErrorNotSupported otherwise): each field's unit width -- the widest of
-// 16/8/4 bytes dividing its row and every pointer -- and units per row.
-static int coop_unit(const void* src, int64_t rb, const void* dst, const void* red) {
-    uintptr_t a = (uintptr_t)src | (uintptr_t)dst | (uintptr_t)rb;
-    if (red) a |= (uintptr_t)red;
-    const int W = (a & 15) == 0 ? 16 : (a & 7) == 0 ? 8 : (a & 3) == 0 ? 4 : 0;
-    if (!W || rb / W > 16) return -1;
-    return W * 32 + (int)(rb / W);
+template <int A, int B, int C, int D>
+static hipError_t launch_coop_fields(const CoopFieldPtrs& fp, const PackJob& j) {
+    const Workspace& ws = j.ws;
+    prof_begin(j.s, K_PACK);
+    // one wave per 64-row round
+    hipLaunchKernelGGL((pack_coop_fields_kernel<A, B, C, D>), dim3((unsigned)ws.tn),
+                       dim3(j.tile_rows), 0, j.s, fp, j.n, (const uint8_t*)j.dest, j.nb,
+                       nbits_for(j.nb), j.drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn,
+                       j.tile_rows, j.redirect_bin, kXcdPackChunk, ws.scan_err, j.side->src,
+                       j.side->dst, j.side->red);
+    prof_end(j.s, K_PACK);
+    return hipGetLastError();
 }
 
+// The cooperative multi-field kernel for a field signature it is built for
+// (hipErrorNotSupported otherwise; coop_unit: each field's unit width and
+// units per row).  j: the tile context and the side field of the pack.
 static hipError_t pack_coop_fields(int nf, const void* const* srcs, const int64_t* row_bytes,
-                                   int64_t n, const void* dest, int nbins, int drop_bin,
-                                   int tile_rows, const Workspace& ws, void* const* dsts,
-                                   int redirect_bin, void* const* reds, hipStream_t s,
-                                   const uint16_t* ids_src, uint16_t* ids_dst, uint16_t* ids_red) {
+                                   void* const* dsts, void* const* reds, const PackJob& j) {
     int u[4] = {0, 0, 0, 0};
     CoopFieldPtrs fp{};
     for (int f = 0; f < nf; ++f) {
@@ -1853,22 +1803,19 @@ static hipError_t pack_coop_fields(int nf, const void* const* srcs, const int64_
     auto sig = [&](int a, int b, int c, int d) { return u[0] == a && u[1] == b && u[2] == c && u[3] == d; };
     constexpr int F4x1 = 4 * 32 + 1, F4x3 = 4 * 32 + 3, F8x1 = 8 * 32 + 1, F8x3 = 8 * 32 + 3,
                   F16x2 = 16 * 32 + 2, F4x9 = 4 * 32 + 9, F16x1 = 16 * 32 + 1, F8x2 = 8 * 32 + 2;
-    const int threads = tile_rows;   // one wave per 64-row round
-#define MGR_PCF(A, B, C, D)                                                                          {                                                                                                    prof_begin(s, K_PACK);                                                                           hipLaunchKernelGGL((pack_coop_fields_kernel<A, B, C, D>), dim3((unsigned)ws.tn),                                     dim3(threads), 0, s, fp, n, (const uint8_t*)dest, nbins,                                          nbits_for(nbins), drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0,                               ws.tn, tile_rows, redirect_bin, kXcdPackChunk, ws.scan_err, ids_src,                              ids_dst, ids_red);                                                             prof_end(s, K_PACK);                                                                             return hipGetLastError();                                                                    }
     // config 5's fields as arrays: pos f32 x3, vel f32 x3, mass f32, id i64
-    if (sig(F4x3, F4x3, F4x1, F8x1)) MGR_PCF(F4x3, F4x3, F4x1, F8x1)
+    if (sig(F4x3, F4x3, F4x1, F8x1)) return launch_coop_fields<F4x3, F4x3, F4x1, F8x1>(fp, j);
     // f64 positions + i64 ids; 32-byte records + their f64 positions (return_positions)
-    if (sig(F8x3, F8x1, 0, 0)) MGR_PCF(F8x3, F8x1, 0, 0)
-    if (sig(F16x2, F8x3, 0, 0)) MGR_PCF(F16x2, F8x3, 0, 0)
+    if (sig(F8x3, F8x1, 0, 0)) return launch_coop_fields<F8x3, F8x1, 0, 0>(fp, j);
+    if (sig(F16x2, F8x3, 0, 0)) return launch_coop_fields<F16x2, F8x3, 0, 0>(fp, j);
     // 36-byte records + their f32 positions (config 5 with return_positions)
-    if (sig(F4x9, F4x3, 0, 0)) MGR_PCF(F4x9, F4x3, 0, 0)
+    if (sig(F4x9, F4x3, 0, 0)) return launch_coop_fields<F4x9, F4x3, 0, 0>(fp, j);
     // positions f32 x3 + ids i64 / f64 x2 + i64
-    if (sig(F4x3, F8x1, 0, 0)) MGR_PCF(F4x3, F8x1, 0, 0)
-    if (sig(F16x1, F8x1, 0, 0)) MGR_PCF(F16x1, F8x1, 0, 0)
-    if (sig(F8x3, F8x3, F8x1, 0)) MGR_PCF(F8x3, F8x3, F8x1, 0)
-    if (sig(F4x3, F4x3, F8x1, 0)) MGR_PCF(F4x3, F4x3, F8x1, 0)
-    if (sig(F8x2, F8x1, 0, 0)) MGR_PCF(F8x2, F8x1, 0, 0)
-#undef MGR_PCF
+    if (sig(F4x3, F8x1, 0, 0)) return launch_coop_fields<F4x3, F8x1, 0, 0>(fp, j);
+    if (sig(F16x1, F8x1, 0, 0)) return launch_coop_fields<F16x1, F8x1, 0, 0>(fp, j);
+    if (sig(F8x3, F8x3, F8x1, 0)) return launch_coop_fields<F8x3, F8x3, F8x1, 0>(fp, j);
+    if (sig(F4x3, F4x3, F8x1, 0)) return launch_coop_fields<F4x3, F4x3, F8x1, 0>(fp, j);
+    if (sig(F8x2, F8x1, 0, 0)) return launch_coop_fields<F8x2, F8x1, 0, 0>(fp, j);
     return hipErrorNotSupported;
 }
 
@@ -1916,15 +1863,8 @@ hipError_t launch_pack_fields(int nf, const void* const* srcs, const int64_t* ro
         // every field in the tile-image kernel when they fit one launch
         int rows = 0;
         PackFieldsArgs fa{};
-        for (const int f : fast) {
-            fa.src[fa.nf] = (const uint8_t*)srcs[f];
-            fa.dst[fa.nf] = (uint8_t*)dsts[f];
-            fa.red[fa.nf] = reds ? (uint8_t*)reds[f] : nullptr;
-            fa.rb[fa.nf] = (int)row_bytes[f];
-            fa.loff[fa.nf] = rows;
-            rows += kFieldsWR * (int)row_bytes[f];
-            ++fa.nf;
-        }
+        for (const int f : fast)
+            rows = fa.add(srcs[f], dsts[f], reds ? reds[f] : nullptr, (int)row_bytes[f], rows);
         fa.wave_lds = rows;
         const int img = align16(tile_rows * max_rb);
         const int lds = img + align16(tile_rows) + nw * fa.wave_lds + nw * 64 * 4;
@@ -1944,9 +1884,10 @@ hipError_t launch_pack_fields(int nf, const void* const* srcs, const int64_t* ro
         tile_rows <= 64 * kCoopMaxRounds && tile_rows / 64 <= 16) {
         // every field in the cooperative multi-field kernel when the fields'
         // signature is one it is built for
-        const hipError_t e = pack_coop_fields(nf, srcs, row_bytes, n, dest, nbins, drop_bin,
-                                              tile_rows, ws, dsts, redirect_bin, reds, s, ids_src,
-                                              ids_dst, ids_red);
+        SideField side{ids_src, ids_dst, ids_red, false};
+        const PackJob j{nullptr, 0, n, dest, nbins, drop_bin, tile_rows, ws, nullptr, redirect_bin,
+                        nullptr, s, &side, h};
+        const hipError_t e = pack_coop_fields(nf, srcs, row_bytes, dsts, reds, j);
         if (e != hipErrorNotSupported) return e;
     }
     size_t i = 0;
@@ -1957,13 +1898,7 @@ hipError_t launch_pack_fields(int nf, const void* const* srcs, const int64_t* ro
             const int f = fast[i];
             const int rb = (int)row_bytes[f];
             if (rows + kFieldsWR * rb > budget) break;
-            fa.src[fa.nf] = (const uint8_t*)srcs[f];
-            fa.dst[fa.nf] = (uint8_t*)dsts[f];
-            fa.red[fa.nf] = reds ? (uint8_t*)reds[f] : nullptr;
-            fa.rb[fa.nf] = rb;
-            fa.loff[fa.nf] = rows;
-            rows += kFieldsWR * rb;   // a multiple of 512 bytes
-            ++fa.nf;
+            rows = fa.add(srcs[f], dsts[f], reds ? reds[f] : nullptr, rb, rows);   // + n * 512 bytes
         }
         fa.wave_lds = rows + kFieldsTail;
         const int lds = nw * 64 * 4 + nw * fa.wave_lds;
@@ -1993,24 +1928,24 @@ static hipError_t launch_pack_rows(const void* src, int64_t row_bytes, int64_t n
                                    const void* dest, int nbins, int drop_bin, int tile_rows,
                                    const Workspace& ws, void* dst, int redirect_bin,
                                    void* redirect_dst, hipStream_t s, SideField* side) {
-    // Widest unit dividing the row and every base address.
-    uintptr_t a = (uintptr_t)src | (uintptr_t)dst | (uintptr_t)row_bytes;
-    if (redirect_dst) a |= (uintptr_t)redirect_dst;
+    // one snapshot of the hooks for the whole launch
+    const PackJob j{src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst, redirect_bin,
+                    redirect_dst, s, side, hooks()};
     // profiler: narrow (< 4-byte) rows apart
     const int kid = row_bytes < 4 ? K_PACK_NARROW : K_PACK;
-    const Hooks& h = hooks();   // one snapshot for the whole launch
     prof_begin(s, kid);
-    hipError_t e = pack_img(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst,
-                            redirect_bin, redirect_dst, s, side, h);
-    if (e != hipErrorNotSupported) {
-        prof_end(s, kid);
-        return e;
+    hipError_t e = pack_img(j);
+    if (e == hipErrorNotSupported) {
+        // the widest unit dividing the row and every base address
+        switch (unit_log((uintptr_t)src | (uintptr_t)dst | (uintptr_t)row_bytes |
+                         (uintptr_t)redirect_dst)) {
+            case 4: e = pack_w<16>(j); break;
+            case 3: e = pack_w<8>(j); break;
+            case 2: e = pack_w<4>(j); break;
+            case 1: e = pack_w<2>(j); break;
+            default: e = pack_w<1>(j); break;
+        }
     }
-    if ((a & 15) == 0) e = pack_w<16>(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s, side, h);
-    else if ((a & 7) == 0) e = pack_w<8>(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s, side, h);
-    else if ((a & 3) == 0) e = pack_w<4>(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s, side, h);
-    else if ((a & 1) == 0) e = pack_w<2>(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s, side, h);
-    else e = pack_w<1>(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst, redirect_bin, redirect_dst, s, side, h);
     prof_end(s, kid);
     return e;
 }

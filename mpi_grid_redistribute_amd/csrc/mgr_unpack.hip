@@ -12,7 +12,6 @@
 namespace mgr {
 
 constexpr int kUnpackCoopRounds = 16;   // cooperative unpack tiles: <= 1024 rows (one wave a round)
-constexpr long long kSlotMask = (1ll << 62) - 1;   // bit 62 of a slot: read redirect_src
 
 // ---------------------------------------------------------------- generic
 // Mirror of pack_kernel: one wave per tile, per-wave LDS goff/run tables, any
@@ -109,7 +108,7 @@ struct CoopGather {
     static constexpr int W = U >> 5, UPR = U & 31;
     using T = typename Unit<(W ? W : 4)>::T;
     T v[UPR ? UPR : 1];
-    // tgt: this lane's row's slot (bit 62: in redirect_src), < 0: a dropped row
+    // tgt: this lane's row's tagged slot (redirect bit: in redirect_src), < 0: a dropped row
     __device__ __forceinline__ void load(const uint8_t* __restrict__ packed,
                                          const uint8_t* __restrict__ red, long long tgt, int nr,
                                          int lane) {
@@ -123,8 +122,8 @@ struct CoopGather {
                 const long long t = __shfl(tgt, r, 64);
                 v[k] = T{};
                 if (u < nr * UPR && t >= 0) {
-                    const T* s = (t >> 62) ? r_u : p_u;
-                    v[k] = s[(t & kSlotMask) * UPR + part];
+                    const T* s = slot_redirected(t) ? r_u : p_u;
+                    v[k] = s[slot_row(t) * UPR + part];
                 }
             }
         }
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(1024) void unpack_coop_kernel(
     const uint32_t* __restrict__ scan_err) {
     __shared__ int s_cnt[kUnpackCoopRounds][64];
     const int w = threadIdx.x >> 6, lane = lane_id();
-    const int64_t tile = t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+    const int64_t tile = tile_index(t0, tn, xcd);
     const int64_t row0 = tile * (int64_t)tile_rows + 64 * w;
     const int nr = (int)max((int64_t)0, min((int64_t)64, n - row0));
     const unsigned b = lane < nr ? (unsigned)dest[row0 + lane] : 0u;
@@ -162,21 +161,14 @@ __global__ __launch_bounds__(1024) void unpack_coop_kernel(
     if (lane < nb) tbase = seg_start(offsets, bin_starts, T, tile, lane, redirect_bin);
     // rank inside the round; lane l counts bin l
     const bool valid = lane < nr;
-    unsigned long long pe = __ballot(valid), mine = pe;
-    for (int i = 0; i < nbits; ++i) {
-        const unsigned long long m = __ballot((b >> i) & 1u);
-        pe &= ((b >> i) & 1u) ? m : ~m;
-        mine &= ((lane >> i) & 1) ? m : ~m;
-    }
-    if (!valid) pe = 0ull;
-    s_cnt[w][lane] = __popcll(mine);
+    unsigned long long pe;
+    s_cnt[w][lane] = round_rank(b, valid, lane, nbits, &pe);
     __syncthreads();
     if (scan_failed(scan_err)) return;
     for (int j = 0; j < w; ++j) tbase += s_cnt[j][lane];
     const long long base = __shfl(tbase, (int)b, 64);
     long long tgt = -1;
-    if (valid && (int)b != drop_bin)
-        tgt = (base + rank_in(pe)) | ((int)b == redirect_bin ? (1ll << 62) : 0ll);
+    if (valid && (int)b != drop_bin) tgt = tag_slot(base + rank_in(pe), (int)b, redirect_bin);
     CoopGather<U0> f0;
     CoopGather<U1> f1;
     CoopGather<U2> f2;
@@ -192,35 +184,30 @@ __global__ __launch_bounds__(1024) void unpack_coop_kernel(
 }
 
 // --------------------------------------------------------------- launchers
-// log2 of the widest copy unit (<= 16 bytes) that divides every address in a
-// (the packs' unit_log rule)
-static inline int unit_log(uintptr_t a) {
-    return (a & 15) == 0 ? 4 : (a & 7) == 0 ? 3 : (a & 3) == 0 ? 2 : (a & 1) == 0 ? 1 : 0;
-}
-
-// A field's cooperative signature W * 32 + UPR -- the widest of 16/8/4 bytes
-// dividing its row and every pointer, <= 16 units per row -- or -1 (the
-// alignment rule of the pack's coop_unit).
-static int coop_unit(const void* packed, int64_t rb, const void* out, const void* red) {
-    uintptr_t a = (uintptr_t)packed | (uintptr_t)out | (uintptr_t)rb;
-    if (red) a |= (uintptr_t)red;
-    const int W = (a & 15) == 0 ? 16 : (a & 7) == 0 ? 8 : (a & 3) == 0 ? 4 : 0;
-    if (!W || rb / W > 16) return -1;
-    return W * 32 + (int)(rb / W);
-}
-
+// (unit widths and field signatures: unit_log, coop_unit of mgr_internal.h)
 static bool coop_shape(int nbins, int tile_rows) {
     return nbins <= 64 && dest_bytes(nbins) == 1 && tile_rows <= 64 * kUnpackCoopRounds;
 }
 
-#define MGR_UCK(A, B, C, D)                                                                    \
-    {                                                                                          \
-        hipLaunchKernelGGL((unpack_coop_kernel<A, B, C, D>), dim3((unsigned)ws.tn),            \
-                           dim3(tile_rows), 0, s, fp, n, (const uint8_t*)dest, nbins,          \
-                           nbits_for(nbins), drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, \
-                           ws.tn, tile_rows, redirect_bin, kXcdPackChunk, ws.scan_err);        \
-        return hipGetLastError();                                                              \
-    }
+// The tile context of an unpack, as the cooperative launchers share it.
+struct UnpackTiles {
+    int64_t n;
+    const void* dest;
+    int nbins, drop_bin, tile_rows;
+    const Workspace& ws;
+    int redirect_bin;
+    hipStream_t s;
+};
+
+template <int A, int B, int C, int D>
+static hipError_t launch_unpack_coop(const UnpackFieldPtrs& fp, const UnpackTiles& t) {
+    const Workspace& ws = t.ws;
+    hipLaunchKernelGGL((unpack_coop_kernel<A, B, C, D>), dim3((unsigned)ws.tn),
+                       dim3(t.tile_rows), 0, t.s, fp, t.n, (const uint8_t*)t.dest, t.nbins,
+                       nbits_for(t.nbins), t.drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0,
+                       ws.tn, t.tile_rows, t.redirect_bin, kXcdPackChunk, ws.scan_err);
+    return hipGetLastError();
+}
 
 // One field through the cooperative kernel (hipErrorNotSupported: not its shape).
 static hipError_t unpack_coop(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
@@ -233,7 +220,8 @@ static hipError_t unpack_coop(const void* packed, int64_t row_bytes, int64_t n, 
     fp.packed[0] = (const uint8_t*)packed;
     fp.red[0] = (const uint8_t*)red;
     fp.out[0] = (uint8_t*)out;
-#define MGR_UC1(W_, N_) case W_ * 32 + N_: MGR_UCK(W_ * 32 + N_, 0, 0, 0)
+    const UnpackTiles t{n, dest, nbins, drop_bin, tile_rows, ws, redirect_bin, s};
+#define MGR_UC1(W_, N_) case W_ * 32 + N_: return launch_unpack_coop<W_ * 32 + N_, 0, 0, 0>(fp, t);
     switch (u) {
         MGR_UC1(16, 1) MGR_UC1(16, 2) MGR_UC1(16, 3) MGR_UC1(16, 4)
         MGR_UC1(8, 1) MGR_UC1(8, 2) MGR_UC1(8, 3) MGR_UC1(8, 4)
@@ -267,19 +255,19 @@ static hipError_t unpack_coop_fields(int nf, const void* const* packed, const in
     auto sig = [&](int a, int b, int c, int d) { return u[0] == a && u[1] == b && u[2] == c && u[3] == d; };
     constexpr int F4x1 = 4 * 32 + 1, F4x3 = 4 * 32 + 3, F8x1 = 8 * 32 + 1, F8x3 = 8 * 32 + 3,
                   F16x2 = 16 * 32 + 2, F4x9 = 4 * 32 + 9, F16x1 = 16 * 32 + 1, F8x2 = 8 * 32 + 2;
+    const UnpackTiles t{n, dest, nbins, drop_bin, tile_rows, ws, redirect_bin, s};
     // the field sets of pack_coop_fields (mgr_pack.hip)
-    if (sig(F4x3, F4x3, F4x1, F8x1)) MGR_UCK(F4x3, F4x3, F4x1, F8x1)
-    if (sig(F8x3, F8x1, 0, 0)) MGR_UCK(F8x3, F8x1, 0, 0)
-    if (sig(F16x2, F8x3, 0, 0)) MGR_UCK(F16x2, F8x3, 0, 0)
-    if (sig(F4x9, F4x3, 0, 0)) MGR_UCK(F4x9, F4x3, 0, 0)
-    if (sig(F4x3, F8x1, 0, 0)) MGR_UCK(F4x3, F8x1, 0, 0)
-    if (sig(F16x1, F8x1, 0, 0)) MGR_UCK(F16x1, F8x1, 0, 0)
-    if (sig(F8x3, F8x3, F8x1, 0)) MGR_UCK(F8x3, F8x3, F8x1, 0)
-    if (sig(F4x3, F4x3, F8x1, 0)) MGR_UCK(F4x3, F4x3, F8x1, 0)
-    if (sig(F8x2, F8x1, 0, 0)) MGR_UCK(F8x2, F8x1, 0, 0)
+    if (sig(F4x3, F4x3, F4x1, F8x1)) return launch_unpack_coop<F4x3, F4x3, F4x1, F8x1>(fp, t);
+    if (sig(F8x3, F8x1, 0, 0)) return launch_unpack_coop<F8x3, F8x1, 0, 0>(fp, t);
+    if (sig(F16x2, F8x3, 0, 0)) return launch_unpack_coop<F16x2, F8x3, 0, 0>(fp, t);
+    if (sig(F4x9, F4x3, 0, 0)) return launch_unpack_coop<F4x9, F4x3, 0, 0>(fp, t);
+    if (sig(F4x3, F8x1, 0, 0)) return launch_unpack_coop<F4x3, F8x1, 0, 0>(fp, t);
+    if (sig(F16x1, F8x1, 0, 0)) return launch_unpack_coop<F16x1, F8x1, 0, 0>(fp, t);
+    if (sig(F8x3, F8x3, F8x1, 0)) return launch_unpack_coop<F8x3, F8x3, F8x1, 0>(fp, t);
+    if (sig(F4x3, F4x3, F8x1, 0)) return launch_unpack_coop<F4x3, F4x3, F8x1, 0>(fp, t);
+    if (sig(F8x2, F8x1, 0, 0)) return launch_unpack_coop<F8x2, F8x1, 0, 0>(fp, t);
     return hipErrorNotSupported;
 }
-#undef MGR_UCK
 
 template <int W, typename DestT, bool kWide>
 static hipError_t unpack_t(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
