@@ -351,11 +351,17 @@ int mgr_partition_by_position(const mgr_plan* plan, void* pos, int pos_dtype, in
  * in mgr_bin_count_fine, else NULL -- from fine_out + b * cap_rows).
  * Positions are wrapped in place as mgr_bin_count does (S1).  bin_counts
  * (int64 [nbins], device) = the rows of every bin; rows at or beyond cap_rows
- * are NOT written, so a count above cap_rows means the caller redoes the
- * partition with the classic path (mgr_bin_count with periodic = 0 re-bins
- * the stored, wrapped positions identically, S2) -- or -1 everywhere when a
- * look-back gave up (nothing written).  Workspace: mgr_onepass_workspace_bytes
- * (zeroed by the call).  MGR_EUNSUPPORTED for shapes it does not take.
+ * are NOT written (a wave whose rows of a bin would reach cap_rows writes none
+ * of them, nor their fine cells), so a count above cap_rows means the caller
+ * redoes the partition with the classic path (mgr_bin_count with periodic = 0
+ * re-bins the stored, wrapped positions identically, S2).
+ * Failure: a tile whose look-back gave up writes no rows and poisons its
+ * prefix; bin_counts is written by the last tile from its own prefix and is
+ * -1 for every bin that prefix found poisoned.  A tile that gave up AFTER later
+ * tiles summed past its aggregate is not reported (the SoA entry point below
+ * reports every such tile; its completion counter measured +0.43 ms on this
+ * kernel).  Workspace: mgr_onepass_workspace_bytes (zeroed by the call).
+ * MGR_EUNSUPPORTED for shapes it does not take.
  * Tail read: the records are staged in 16-byte units from the 16-byte-aligned
  * data, so the last unit may READ up to 12 bytes past the array's end, inside
  * its aligned 16-byte unit (never written, never used).                    */

@@ -33,7 +33,9 @@ extern "C" {
  * -1 = none), "fields_kernel" (multi-field packs: 0 the product's choice,
  * 1 the per-wave LDS-image kernel, 2 the tile-image kernel, 3 the
  * cooperative kernel -- each where it takes the fields, else the next),
- * "onepass_poison_tile" (mgr_partition_onepass_fields: the tile with this
+ * "onepass_poison_tile" (mgr_partition_onepass_fields, and the shared
+ * look-back of mgr_partition_onepass, whose counts report it only as far as
+ * its poisoned prefix is met: the tile with this
  * ticket treats its look-back as given up -- it publishes its prefix
  * poisoned and writes no rows: a deterministic failed partition, -1 = none),
  * "msel_wide" (1: mgr_msel_pack* run the wide multi-selection kernel also

@@ -210,8 +210,8 @@ struct Hooks {
     int scan_poison_chunk = -1;   // >= 0: that scan chunk publishes poisoned (a failed scan)
     int fields_kernel = 0;        // multi-field packs: 0 product choice, 1 per-wave image,
                                   // 2 tile image, 3 cooperative (where they take the fields)
-    int onepass_poison_tile = -1; // >= 0: the multi-field one-pass tile with that ticket treats
-                                  // its look-back as given up (a failed partition)
+    int onepass_poison_tile = -1; // >= 0: the one-pass tile (records or fields) with that ticket
+                                  // treats its look-back as given up (a failed partition)
     int msel_wide = 0;            // 1: the wide multi-selection pack also for 1..3 fields
     int unpack_kernel = 0;        // unpacks: 0 product choice, 1 generic (wave per tile), 2
                                   // cooperative single-field (field sets go field by field)

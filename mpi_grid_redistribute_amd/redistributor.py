@@ -1257,6 +1257,29 @@ class GridPartitioner:
                   _ptrs([o.data_ptr() for o in outs]), -1, None, 0, -1, _lib.stream_handle(stream))
         return outs
 
+    def _onepass_state(self, n, cap_rows, fine_cells, out_row_bytes, key_of):
+        """What both one-pass entry points keep for the next call of the same
+        shape: (cap, workspace, one output per entry of ``out_row_bytes``,
+        fine ids or None, counts, fine plan or None).  ``cap_rows`` defaults
+        to 1.25 x the mean + 4096 rows per bin region; ``key_of(cap)`` is the
+        shape's key in the single-entry cache.  The counts become
+        ``last_counts``."""
+        cap = int(cap_rows) if cap_rows is not None else (5 * n) // (4 * self.nbins) + 4096
+        key = key_of(cap)
+        if key not in self._cache:
+            wsb = _lib.load().mgr_onepass_workspace_bytes(n, self.nbins)
+            ws = torch.empty(max(int(wsb), 8), dtype=torch.uint8, device=self._dev)
+            outs = [torch.empty(max(self.nbins * cap * b, 1), dtype=torch.uint8, device=self._dev)
+                    for b in out_row_bytes]
+            fo = (torch.empty(max(self.nbins * cap, 1), dtype=torch.int16, device=self._dev)
+                  if fine_cells is not None else None)
+            counts = torch.empty(self.nbins, dtype=torch.int64, device=self._dev)
+            self._cache = {key: (ws, outs, fo, counts)}
+        ws, outs, fo, counts = self._cache[key]
+        self.last_counts = counts
+        fplan = self._fine_plan(fine_cells) if fine_cells is not None else None
+        return cap, ws, outs, fo, counts, fplan
+
     def partition_onepass_device(self, data_flat, row_bytes, pos_tensor, periodic=True,
                                  stream=None, fine_cells=None, cap_rows=None):
         """The local stage in ONE read of the records (mgr_partition_onepass):
@@ -1277,20 +1300,9 @@ class GridPartitioner:
         if n and (pos_tensor.stride(0) * esz != row_bytes or pos_tensor.stride(1) != 1
                   or off < 0 or off + 3 * esz > row_bytes):
             raise ValueError("pos_tensor must be the position view inside the records")
-        cap = int(cap_rows) if cap_rows is not None else (5 * n) // (4 * self.nbins) + 4096
-        key = ("onepass", n, int(row_bytes), cap, fine_cells is not None)
-        if key not in self._cache:
-            wsb = _lib.load().mgr_onepass_workspace_bytes(n, self.nbins)
-            ws = torch.empty(max(int(wsb), 8), dtype=torch.uint8, device=self._dev)
-            out = torch.empty(max(self.nbins * cap * int(row_bytes), 1), dtype=torch.uint8,
-                              device=self._dev)
-            fo = (torch.empty(max(self.nbins * cap, 1), dtype=torch.int16, device=self._dev)
-                  if fine_cells is not None else None)
-            counts = torch.empty(self.nbins, dtype=torch.int64, device=self._dev)
-            self._cache = {key: (ws, out, fo, counts)}
-        ws, out, fo, counts = self._cache[key]
-        self.last_counts = counts
-        fplan = self._fine_plan(fine_cells) if fine_cells is not None else None
+        cap, ws, (out,), fo, counts, fplan = self._onepass_state(
+            n, cap_rows, fine_cells, [int(row_bytes)],
+            lambda cap: ("onepass", n, int(row_bytes), cap, fine_cells is not None))
         _lib.call("mgr_partition_onepass", self._plan.h, fplan.h if fplan else None,
                   _lib.ptr(data_flat), int(row_bytes), int(off), pos_code(pos_tensor.dtype), n,
                   int(bool(periodic)), _lib.ptr(out), _lib.ptr(fo), cap, _lib.ptr(counts),
@@ -1349,20 +1361,9 @@ class GridPartitioner:
             pf = nf
             srcs.append(pos_tensor.data_ptr())
             rbs.append(prb)
-        cap = int(cap_rows) if cap_rows is not None else (5 * n) // (4 * self.nbins) + 4096
-        key = ("onepass_fields", n, tuple(rbs), cap, fine_cells is not None, pf, extra)
-        if key not in self._cache:
-            wsb = _lib.load().mgr_onepass_workspace_bytes(n, self.nbins)
-            ws = torch.empty(max(int(wsb), 8), dtype=torch.uint8, device=self._dev)
-            outs = [torch.empty(max(self.nbins * cap * b, 1), dtype=torch.uint8, device=self._dev)
-                    for b in rbs[:nf]]
-            fo = (torch.empty(max(self.nbins * cap, 1), dtype=torch.int16, device=self._dev)
-                  if fine_cells is not None else None)
-            counts = torch.empty(self.nbins, dtype=torch.int64, device=self._dev)
-            self._cache = {key: (ws, outs, fo, counts)}
-        ws, outs, fo, counts = self._cache[key]
-        self.last_counts = counts
-        fplan = self._fine_plan(fine_cells) if fine_cells is not None else None
+        cap, ws, outs, fo, counts, fplan = self._onepass_state(
+            n, cap_rows, fine_cells, rbs[:nf],
+            lambda cap: ("onepass_fields", n, tuple(rbs), cap, fine_cells is not None, pf, extra))
         _lib.call("mgr_partition_onepass_fields", self._plan.h, fplan.h if fplan else None,
                   len(srcs), _ptrs(srcs), _i64s(rbs), pf, int(off), pos_code(pos_tensor.dtype), n,
                   int(bool(periodic)), _ptrs([o.data_ptr() for o in outs] + [0] * extra),
