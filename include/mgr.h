@@ -475,6 +475,24 @@ int mgr_msel_pack_fields(int nfields, const void* const* srcs, const int64_t* ro
 int mgr_msel_pack_placed(int nfields, const void* const* srcs, const int64_t* row_bytes, int64_t n,
                          const uint16_t* flags, int nsets, const int* masks, int tile_rows,
                          const void* workspace, void* const* dsts, int64_t cap_rows, void* stream);
+/* The halo's return path: the inverse of mgr_msel_pack with an add.  acc: n
+ * rows of ncomp elements of type elem.  For every row r and every set k in
+ * ascending order with srcs[k] != NULL (nsets device pointers) and
+ * (flags[r] & masks[k]) == masks[k]:
+ *     acc[r * ncomp + c] += srcs[k][rank_k(r) * ncomp + c],  c < ncomp,
+ * rank_k(r) = the place mgr_msel_pack gives row r in set k.  flags, masks,
+ * tile_rows and workspace are exactly what the forward mgr_msel_count +
+ * mgr_scan used: nothing is counted or scanned again.  Rows in no live set
+ * are neither read nor written.  One add per set in the element type, k
+ * ascending (integers wrap): results are bit-reproducible and equal a
+ * sequential model in the same type.  A workspace whose scan failed leaves
+ * acc untouched.  MGR_EINVAL: nsets outside 1..32, ncomp < 1, an unknown
+ * elem, n < 0, or for n > 0 a null acc / flags / workspace / srcs; n == 0
+ * reads nothing.                                                           */
+typedef enum { MGR_ELEM_F32, MGR_ELEM_F64, MGR_ELEM_I32, MGR_ELEM_I64 } mgr_elem_t;
+int mgr_msel_unpack_add(void* acc, int elem, int ncomp, int64_t n, const uint16_t* flags,
+                        int nsets, const int* masks, int tile_rows, const void* workspace,
+                        const void* const* srcs, void* stream);
 
 /* ------------------------------------------------------------ exchange --
  * Replaces comm.alltoall(send_buff) + np.concatenate (redist.py:199):

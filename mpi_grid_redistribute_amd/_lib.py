@@ -23,6 +23,8 @@ MGR_F16, MGR_I8, MGR_I16, MGR_U8, MGR_U16, MGR_U32, MGR_U64, MGR_B8 = 5, 6, 7, 8
 # element bytes of the position dtypes (mgr_bin_count & co.)
 POS_ITEMSIZE = {MGR_F16: 2, MGR_F32: 4, MGR_F64: 8, MGR_I8: 1, MGR_I16: 2, MGR_I32: 4,
                 MGR_I64: 8, MGR_U8: 1, MGR_U16: 2, MGR_U32: 4, MGR_U64: 8, MGR_B8: 1}
+# element types of mgr_msel_unpack_add (mgr.h mgr_elem_t)
+MGR_ELEM_F32, MGR_ELEM_F64, MGR_ELEM_I32, MGR_ELEM_I64 = 0, 1, 2, 3
 UNIQUE_ID_BYTES = 128
 MAX_FIELDS = 16                      # mgr.h MGR_MAX_FIELDS: fields of a SoA payload
 MSEL_MAX_FIELDS = MAX_FIELDS + 2     # mgr.h MGR_MSEL_MAX_FIELDS: + positions + face flags
@@ -76,6 +78,7 @@ SIGNATURES = {
     "mgr_msel_pack": (_I, [_P, _I64, _I64, _P, _I, _P, _I, _P, _P, _P]),
     "mgr_msel_pack_fields": (_I, [_I, _P, _P, _I64, _P, _I, _P, _I, _P, _P, _P]),
     "mgr_msel_pack_placed": (_I, [_I, _P, _P, _I64, _P, _I, _P, _I, _P, _P, _I64, _P]),
+    "mgr_msel_unpack_add": (_I, [_P, _I, _I, _I64, _P, _I, _P, _I, _P, _P, _P]),
     "mgr_group_p2p": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "mgr_comm_unique_id": (_I, [_P]),
     "mgr_comm_create": (_I, [_P, _I, _I, ctypes.POINTER(_P)]),

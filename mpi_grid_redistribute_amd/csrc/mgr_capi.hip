@@ -496,6 +496,23 @@ int mgr_msel_pack_placed(int nfields, const void* const* srcs, const int64_t* ro
     return MGR_OK;
 }
 
+int mgr_msel_unpack_add(void* acc, int elem, int ncomp, int64_t n, const uint16_t* flags,
+                        int nsets, const int* masks, int tile_rows, const void* workspace,
+                        const void* const* srcs, void* stream) {
+    int rc = check_tile(tile_rows);
+    if (rc || (rc = check_sets(nsets, masks))) return rc;
+    if (ncomp < 1) return fail(MGR_EINVAL, "ncomp %d", ncomp);
+    if (elem < MGR_ELEM_F32 || elem > MGR_ELEM_I64)
+        return fail(MGR_EINVAL, "elem %d (MGR_ELEM_F32 / F64 / I32 / I64)", elem);
+    if (n < 0) return fail(MGR_EINVAL, "n < 0");
+    if (n > 0 && (!acc || !flags || !workspace || !srcs)) return fail(MGR_EINVAL, "null argument");
+    if (n == 0) return MGR_OK;
+    const mgr::Workspace ws = mgr::carve((void*)workspace, n, nsets, tile_rows);
+    HIP_OK(mgr::launch_msel_unpack_add(acc, elem, ncomp, n, flags, nsets, masks, tile_rows, ws,
+                                       srcs, (hipStream_t)stream));
+    return MGR_OK;
+}
+
 int mgr_count_ids(const uint16_t* ids, int64_t n, int nbins, int tile_rows, void* dest,
                   uint32_t* bad_ids, void* workspace, void* stream) {
     int rc = check_tile(tile_rows);

@@ -114,6 +114,12 @@ hipError_t launch_msel_pack(int nfields, const void* const* srcs, const int64_t*
                             int64_t n, const uint16_t* flags, int nsets, const int* masks,
                             int tile_rows, const Workspace& ws, void* const* dsts, hipStream_t s,
                             int64_t cap_rows = -1);
+// The halo's return path (mgr_msel_unpack.hip): acc[r] += srcs[k][rank_k(r)]
+// for the ranks of launch_msel_pack with the same flags, masks and workspace.
+hipError_t launch_msel_unpack_add(void* acc, int elem, int ncomp, int64_t n,
+                                  const uint16_t* flags, int nsets, const int* masks,
+                                  int tile_rows, const Workspace& ws, const void* const* srcs,
+                                  hipStream_t s);
 hipError_t launch_count_ids(const uint16_t* ids, int64_t n, int nbins, int tile_rows,
                             const Workspace& ws, void* dest, uint32_t* bad, hipStream_t s);
 hipError_t launch_rank_ids(const uint16_t* ids, int64_t n, int nbins, int tile_rows,

@@ -120,8 +120,49 @@ def self_halo_pieces(dim):
     return buf
 
 
+class HaloRoute:
+    """What ``reduce_overload`` needs to sum per-row results on overload rows
+    back onto the rows they are copies of (``exchange_overload(...,
+    return_route=True)``): everything the forward exchange left on the device
+    and read on the host, so the way back bins, scans and counts nothing.
+
+      * the local rows' face flags (2 B/row) and their selection handle (masks
+        and the msel workspace as mgr_scan left it);
+      * per dimension: the buffer's selection handle (its own workspace, the
+        flags of the rows received so far), the neighbours, and the host-side
+        sizes ``nla, nlb, nga, ngb`` (sent: local / buffer piece to a / b),
+        ``rla, rga, rlb, rgb`` (received), ``ia, ib`` (where the received
+        pieces were appended) and ``m`` (buffer rows before the dimension);
+      * on the one-rank path the one selection handle over the 3^dim - 1
+        pieces and the piece sizes.
+
+    Buffers that came from a Scratch are TAKEN OUT of it (the next exchange
+    allocates anew), so a route stays valid across later calls and may be
+    used any number of times.  Memory per live route: about 2 * (n_local +
+    n_halo) bytes of flags plus the msel workspaces (12 bytes per (set, tile
+    of 4096 rows), + 32 KiB each).  Freed by ``release()``."""
+
+    def __init__(self, owner, n_local, n_halo, flags, lh=None, nb=None, selfd=None, steps=None,
+                 self_handle=None, self_counts=None):
+        self._owner = owner
+        self.n_local, self.n_halo = int(n_local), int(n_halo)
+        self._flags, self._lh = flags, lh
+        self._nb, self._selfd, self._steps = nb, selfd, steps
+        self._self, self._self_counts = self_handle, self_counts
+        self._live = True
+
+    @property
+    def released(self):
+        return not self._live
+
+    def release(self):
+        """Free the route's device memory; it cannot be used afterwards."""
+        self._flags = self._lh = self._steps = self._self = None
+        self._live = False
+
+
 def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, pending=(),
-               multi=False):
+               multi=False, owner=None):
     """exchange_overload when every neighbour is this rank: all pieces are
     known from the local rows' flags, so one selection pass counts them all
     and one multi-set pack writes every row straight to each of its pieces
@@ -139,7 +180,12 @@ def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, 
 
     def result(out, total, in_arena):
         data = out[:D] if multi else out[0]
-        return data, (out[D] if carry_pos else None), total, in_arena
+        res = data, (out[D] if carry_pos else None), total, in_arena
+        if owner is None:
+            return res
+        sel.take("msel_ws_self")   # the route owns the workspace from here on
+        return res + (HaloRoute(owner, n, total, flags, self_handle=h,
+                                self_counts=np.asarray(counts, dtype=np.int64).copy()),)
 
     def nothing(in_arena):
         empty = torch.empty(0, dtype=torch.uint8, device=dev)
@@ -238,6 +284,20 @@ class DeviceSelect:
             return self.scratch.get(name, nbytes)
         return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.dev)
 
+    def take(self, name):
+        """Buffer ``name`` leaves the scratch (a route owns it from here on)."""
+        if self.scratch is not None:
+            self.scratch.take(name)
+
+    def msel_unpack_add(self, handle, acc_flat, elem, ncomp, srcs):
+        """The inverse of msel_pack with an add (mgr_msel_unpack_add): for
+        every set k with srcs[k] not None, in ascending order, the rows of
+        ``acc_flat`` in the set += srcs[k]'s rows, in row order."""
+        n, flags, cb, k, ws, tile_rows = handle
+        ptrs = (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in srcs])
+        _lib.call("mgr_msel_unpack_add", _lib.ptr(acc_flat), int(elem), int(ncomp), n,
+                  _lib.ptr(flags), k, cb, tile_rows, _lib.ptr(ws), ptrs, _lib.stream_handle())
+
     def flags(self, pos_flat, n, ncols, code, dim, hi, lo):
         f = torch.empty(max(n, 1), dtype=torch.int16, device=self.dev)
         h = np.ascontiguousarray(hi, dtype=np.float64)
@@ -316,7 +376,7 @@ class DeviceSelect:
 
 def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n,
                       overload_lengths, periodic=True, sel=None, arena=None, flags=None,
-                      pending=()):
+                      pending=(), return_route=False):
     """Overload rows of rank R (redist.py:202-309).  ``data_flat``: flat uint8
     tensor of this rank's n payload rows of ``rbd`` bytes; ``pos_flat``: their
     positions (n, ncols) rows of any position dtype (ncols >= dim), or None when the
@@ -336,7 +396,11 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     payload field (at most MAX_FIELDS); every field moves with the same
     selections -- one count and one pack launch per step for all of them,
     one message group per dimension.  ``arena[0]`` is then a list of stores
-    and the returned overload data a list in the same order."""
+    and the returned overload data a list in the same order.
+
+    ``return_route``: a HaloRoute for ``reduce_overload`` is appended to the
+    result; every dimension's buffer selection then keeps a workspace of its
+    own.  Without it the call allocates, copies and launches nothing more."""
     dim = R.dim
     assert len(overload_lengths) == dim, \
         "Overload lengths must be the same length as the dimensions"  # redist.py:245
@@ -358,15 +422,22 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     rbs = rbds + ([ncols * isz] if carry_pos else []) + [2]
     F, FL = len(rbs), len(rbs) - 1                        # fields; the flags field
 
+    steps = []                                            # per dimension, for the route
+
     def result(out, rows, in_arena):
         """out: the fields' overload rows (payload, then positions)."""
-        return (out[:D] if multi else out[0]), (out[D] if carry_pos else None), rows, in_arena
+        res = (out[:D] if multi else out[0]), (out[D] if carry_pos else None), rows, in_arena
+        if not return_route:
+            return res
+        for name in ["msel_ws_local"] + [f"msel_ws_ghost{d}" for d in range(dim)]:
+            sel.take(name)   # the route owns the workspaces from here on
+        return res + (HaloRoute(R, n, rows, flags, lh=lh, nb=nb, selfd=selfd, steps=steps),)
     me = transport.rank
     nb = [neighbours(R, d, periodic) for d in range(dim)]
     selfd = [a == me and b == me for a, b, _, _ in nb]
     if dim <= 3 and all(selfd) and all(ka and kb for _, _, ka, kb in nb):
         return _self_halo(transport, sel, srcs[:F - 1], rbs[:F - 1], flags, n, dim, carry_pos,
-                          arena, dev, pending, multi)
+                          arena, dev, pending, multi, R if return_route else None)
     for c in pending:   # (the general path reads them here)
         check_counts(c.cpu().numpy(), [])
 
@@ -479,7 +550,8 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
             send_g = torch.zeros(2, dtype=torch.int64, device=dev)
             recv_g = torch.zeros(2, dtype=torch.int64, device=dev)
             if m:
-                gh, gcount = sel.msel(store(FL, 0, m).view(torch.int16), m, [sa, sb], "_ghost")
+                gh, gcount = sel.msel(store(FL, 0, m).view(torch.int16), m, [sa, sb],
+                                      f"_ghost{d}" if return_route else "_ghost")
                 send_g.copy_(_encode_counts(gcount))
             if failed:   # keep announcing it: the neighbours' neighbours learn too
                 send_g.fill_(_FAIL)
@@ -506,6 +578,9 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
         ensure(new_m)
         # concat(buffer, from_a, from_b) (redist.py:305): appended in place
         ia, ib = m, m + rla + rga
+        if return_route:
+            steps.append(dict(nla=nla, nlb=nlb, nga=nga, ngb=ngb, rla=rla, rga=rga, rlb=rlb,
+                              rgb=rgb, ia=ia, ib=ib, m=m, gh=gh))
         if selfd[d] and d > 0:
             pack_local([d], {d: (ia, ib)})
         gsz = nga + ngb
@@ -547,3 +622,101 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     if not m:
         return result([torch.empty(0, dtype=torch.uint8, device=dev)] * (F - 1), 0, in_arena)
     return result([store(f, 0, m) for f in range(F - 1)], m, in_arena)
+
+
+ELEM_BYTES = {_lib.MGR_ELEM_F32: 4, _lib.MGR_ELEM_F64: 8, _lib.MGR_ELEM_I32: 4,
+              _lib.MGR_ELEM_I64: 8}
+
+
+def reduce_overload(R, transport, route, local_acc, halo_vals, elem, ncomp, sel=None):
+    """The halo exchange that made ``route``, backwards, with a sum: every
+    value on an overload row is added onto the row it is a copy of, on the
+    rank that owns it.  ``local_acc``: flat uint8 device tensor of
+    route.n_local rows of ``ncomp`` elements of type ``elem`` (_lib.MGR_ELEM_*)
+    -- the output, holding the owner's own values (or zeros) on entry;
+    ``halo_vals``: the same for the route.n_halo overload rows, never written.
+    All three may be lists, one entry per field: the fields then share every
+    message group (one mgr_msel_unpack_add call per field and step).
+
+    The dimensions go backwards, d = dim-1 .. 0, each step mirroring the
+    forward one.  The halo values are copied once into a scratch store S; the
+    rows S[ia : ia + rla + rga] a sent go back to a and S[ib : ...] to b --
+    contiguous, nothing is packed -- while the values for this rank's own
+    to_a sends (nla local + nga buffer rows) come back from a and for its to_b
+    sends from b: the forward sizes with sender and receiver swapped, so no
+    count message and no host sync.  Then two adds: onto ``local_acc`` with the
+    local selection (sets 2d, 2d+1), onto S[0 : m_d] with the dimension's
+    buffer selection.  The rows appended in dimension d - 1 have then absorbed
+    what came through dimension d: corner and edge contributions reach the
+    owner through the same chain of neighbours they were copied along.  A
+    dimension whose neighbours are this rank sends nothing: the sources are
+    the regions of S themselves.  A side that did not send (a non-periodic
+    boundary) gets no source.  The one-rank path is one launch: piece k of
+    ``halo_vals`` onto the rows of piece k's mask.
+
+    Every row's adds come in a fixed order (dimension by dimension, within a
+    launch by ascending set), so a result is bit-identical from run to run."""
+    multi = isinstance(local_acc, (list, tuple))
+    accs, vals = (list(local_acc), list(halo_vals)) if multi else ([local_acc], [halo_vals])
+    elems = list(elem) if multi else [elem]
+    ncomps = list(ncomp) if multi else [ncomp]
+    ebs = [int(c) * ELEM_BYTES[e] for c, e in zip(ncomps, elems)]
+    nf = len(accs)
+    dev = accs[0].device
+    sel = sel or DeviceSelect(dev)
+    if route._self is not None:
+        counts = route._self_counts
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        if not counts.any():
+            return
+        for f in range(nf):
+            srcs = [vals[f][int(offs[k]) * ebs[f]:] if counts[k] else None
+                    for k in range(len(counts))]
+            sel.msel_unpack_add(route._self, accs[f], elems[f], ncomps[f], srcs)
+        return
+    steps, dim = route._steps, len(route._steps)
+    if not route.n_halo and not any(s["nla"] + s["nlb"] for s in steps):
+        return
+    nst = max([s["nla"] + s["nga"] + s["nlb"] + s["ngb"] for s in steps] + [1])
+    S, stage = [], []
+    for f in range(nf):
+        S.append(sel._buf(f"halo_red_store{f}", route.n_halo * ebs[f]))
+        S[f][: route.n_halo * ebs[f]].copy_(vals[f][: route.n_halo * ebs[f]])
+        stage.append(sel._buf(f"halo_red_stage{f}", nst * ebs[f]))
+    for d in range(dim - 1, -1, -1):
+        s = steps[d]
+        a, b = route._nb[d][0], route._nb[d][1]
+        nla, nlb, nga, ngb = s["nla"], s["nlb"], s["nga"], s["ngb"]
+        ia, ib, na, nb_ = s["ia"], s["ib"], s["nla"] + s["nga"], s["nlb"] + s["ngb"]
+        back_a, back_b = s["rla"] + s["rga"], s["rlb"] + s["rgb"]
+        if not route._selfd[d]:
+            # the forward messages with sender and receiver swapped; towards a
+            # pair of ranks the sends and the receives match in posting order
+            # (a == b on a grid extent of 2)
+            ops = []
+            for f in range(nf):
+                eb = ebs[f]
+                if back_b:
+                    ops.append(("send", b, S[f][ib * eb:(ib + back_b) * eb]))
+                if na:
+                    ops.append(("recv", a, stage[f][: na * eb]))
+                if back_a:
+                    ops.append(("send", a, S[f][ia * eb:(ia + back_a) * eb]))
+                if nb_:
+                    ops.append(("recv", b, stage[f][na * eb:(na + nb_) * eb]))
+            _p2p(transport, ops)
+        for f in range(nf):
+            eb = ebs[f]
+            if route._selfd[d]:   # step 1 (to a = me) landed at ib, step 2 at ia
+                la, ga = S[f][ib * eb:], S[f][(ib + nla) * eb:]
+                lb, gb = S[f][ia * eb:], S[f][(ia + nlb) * eb:]
+            else:
+                la, ga = stage[f], stage[f][nla * eb:]
+                lb, gb = stage[f][na * eb:], stage[f][(na + nlb) * eb:]
+            if nla or nlb:
+                srcs = [None] * (2 * dim)
+                srcs[2 * d], srcs[2 * d + 1] = (la if nla else None), (lb if nlb else None)
+                sel.msel_unpack_add(route._lh, accs[f], elems[f], ncomps[f], srcs)
+            if nga or ngb:
+                sel.msel_unpack_add(s["gh"], S[f][: s["m"] * eb], elems[f], ncomps[f],
+                                    [ga if nga else None, gb if ngb else None])

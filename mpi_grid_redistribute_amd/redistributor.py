@@ -41,7 +41,8 @@ from ._arrays import Positions, Rows, box_dtype_code, device, id_array, pos_code
 from .comm import SelfComm, as_transport
 from .exchange import (check_counts, exchange, exchange_back, exchange_pipelined, host_read_start,
                        host_read_wait)
-from .halo import DeviceSelect, exchange_overload, halo_capacity, thresholds
+from .halo import (DeviceSelect, HaloRoute, exchange_overload, halo_capacity, reduce_overload,
+                   thresholds)
 
 
 _WRITE_BACK = {"changed": _lib.MGR_WRITE_BACK_CHANGED, "all": _lib.MGR_WRITE_BACK_ALL}
@@ -451,15 +452,24 @@ class Route:
     -- so a route stays valid across later calls and may be used any number
     of times.  Memory per live route: about n_source * mgr_dest_bytes(nbins) +
     mgr_workspace_bytes(n_source, nbins, tile_rows) bytes (1-2 bytes per row
-    plus 12 bytes per (bin, tile)), freed by ``release()``."""
+    plus 12 bytes per (bin, tile)), freed by ``release()``.  ``halo``: the
+    HaloRoute of a call with ``overload_lengths`` and ``reduce_route=True``
+    (else None); ``n_halo`` the overload rows that call appended after the
+    ``n_local`` redistributed ones.  ``release()`` releases both."""
 
-    def __init__(self, owner, dest, ws, tile_rows, nbins, drop_bin, n_source, layout):
+    def __init__(self, owner, dest, ws, tile_rows, nbins, drop_bin, n_source, layout, halo=None):
         self._owner = owner
         self._dest, self._ws = dest, ws
         self.tile_rows, self.nbins, self.drop_bin = int(tile_rows), int(nbins), int(drop_bin)
         self.n_source = int(n_source)
         self.n_local = int(layout.total_recv)
         self.layout = layout
+        self.halo = halo
+
+    @property
+    def n_halo(self):
+        """Overload rows appended after the n_local rows (0 without a halo)."""
+        return self.halo.n_halo if self.halo is not None else 0
 
     @property
     def send_counts(self):
@@ -476,8 +486,25 @@ class Route:
         return self._ws is None
 
     def release(self):
-        """Free the route's device memory; it cannot be used afterwards."""
+        """Free the route's device memory (its halo route's too); it cannot be
+        used afterwards."""
         self._dest = self._ws = None
+        if self.halo is not None:
+            self.halo.release()
+
+
+# reduce_overload's element types: numpy / torch dtype -> (mgr_elem_t, numpy dtype)
+_REDUCE_ELEMS = {"float32": _lib.MGR_ELEM_F32, "float64": _lib.MGR_ELEM_F64,
+                 "int32": _lib.MGR_ELEM_I32, "int64": _lib.MGR_ELEM_I64}
+
+
+def _reduce_elem(f, what):
+    """(mgr_elem_t, ncomp) of a Rows field, or TypeError naming the four types."""
+    name = str(f.dtype).replace("torch.", "")
+    if name not in _REDUCE_ELEMS:
+        raise TypeError(f"{what}: dtype {f.dtype} cannot be reduced (float32, float64, int32 "
+                        "or int64)")
+    return _REDUCE_ELEMS[name], max(int(np.prod(f.trailing, dtype=np.int64)), 1)
 
 
 def exchange_chunks_for(size, row_bytes):
@@ -596,7 +623,8 @@ class MPIGridRedistributor:
 
     # ------------------------------------------------- redistribution (L2)
     def redistribute_by_position(self, data, position, periodic=True, overload_lengths=None,
-                                 return_positions=False, fine_cells=None, return_route=False):
+                                 return_positions=False, fine_cells=None, return_route=False,
+                                 reduce_route=False):
         """redist.py:115-166.  Returns the rows of ``data`` whose position
         falls in this rank's cell, from every rank, in source-rank order;
         ``position`` is wrapped in place when periodic (S1).  ``data`` may be
@@ -613,15 +641,35 @@ class MPIGridRedistributor:
         offsets) with ``fine_cells``; ``data`` is the tuple of fields for a
         SoA payload.  ``return_route``: (result, route) -- ``result`` is what
         the call returns otherwise, ``route`` a Route for ``return_to_source``
-        (not with ``overload_lengths``: halo rows are copies, their return is
-        a reduction; not with ``fine_cells`` in this one call: redistribute
-        with ``return_route=True``, then ``fine_cell_sort(...,
-        return_route=True)``, and give both routes to ``return_to_source(
-        values, route, sort_route=...)``)."""
+        (rows of any dtype go back one to one).  Not with ``overload_lengths``:
+        halo rows are copies and their return is a reduction, a different
+        contract, which ``reduce_route=True`` selects: (result, route) where
+        the Route also holds the halo exchange's HaloRoute (``route.halo``;
+        ``route.n_local`` redistributed rows, ``route.n_halo`` appended
+        overload rows).  ``return_to_source`` then takes values of n_local +
+        n_halo rows (the layout this call returned) of float32, float64, int32
+        or int64, sums every overload row's value onto the row it is a copy of
+        (``reduce_overload``) and sends the n_local sums home;
+        ``route.release()`` releases both.  (The same in separate calls:
+        ``return_positions=True, return_route=True``, then
+        ``exchange_overload_by_position(..., return_route=True)``,
+        ``reduce_overload`` and ``return_to_source``.)  Not with ``fine_cells``
+        in this one call: redistribute with ``return_route=True``, then
+        ``fine_cell_sort(..., return_route=True)``, and give both routes to
+        ``return_to_source(values, route, sort_route=...)``."""
+        if reduce_route and (overload_lengths is None or fine_cells is not None or return_route):
+            raise ValueError("reduce_route=True goes with overload_lengths alone (no fine_cells, "
+                             "no return_route): it is the route of a call with a halo")
         if return_route and (overload_lengths is not None or fine_cells is not None):
             raise NotImplementedError(
                 "return_route together with overload_lengths or fine_cells: halo rows are "
-                "copies (their return is a reduction onto the owners); for fine_cells use the "
+                "copies, their return is a reduction onto the owners -- with overload_lengths "
+                "pass reduce_route=True (return_to_source then takes n_local + n_halo values "
+                "and sums the halo part onto the owners), or call "
+                "redistribute_by_position(..., return_positions=True, return_route=True), "
+                "exchange_overload_by_position(..., return_route=True), "
+                "reduce_overload(halo_values, halo_route, local_values=...) and "
+                "return_to_source(sums, route); for fine_cells use the "
                 "two-call route -- redistribute_by_position(..., return_positions=True, "
                 "return_route=True), then fine_cell_sort(..., return_route=True), then "
                 "return_to_source(values, route, sort_route=...)")
@@ -648,7 +696,7 @@ class MPIGridRedistributor:
                     "the result, and concatenate the two per field")
             self._check_halo(overload_lengths)
             return self._redistribute_halo(data, position, fields[0], pos, periodic,
-                                           overload_lengths, return_positions)
+                                           overload_lengths, return_positions, reduce_route)
         nd = len(fields)
         run_fields = list(fields) + ([None] if return_positions else [])
 
@@ -713,31 +761,47 @@ class MPIGridRedistributor:
         return_route=True)`` on the rows the route delivered): ``values`` are
         in fine-cell order; they are unsorted straight into the buffers the
         reverse exchange sends from (one mgr_unpack_ranked_fields launch, no
-        further copy)."""
+        further copy).  A route of a call with ``overload_lengths`` and
+        ``reduce_route=True`` (``route.halo``): ``values`` have ``route.n_local
+        + route.n_halo`` rows, the layout that call returned, of float32,
+        float64, int32 or int64; the halo part is first summed onto the rows it
+        copies (``reduce_overload``), so original row i gets its own value
+        plus the values of all its overload copies."""
         if not isinstance(route, Route):
             raise TypeError("route: a Route of redistribute_by_position(..., return_route=True)")
         if route.released:
             raise ValueError("the route was released")
-        o = route._owner
-        if o is not self and (o.size != self.size or o.rank != self.rank
-                              or not np.array_equal(o.grid_topology, self.grid_topology)
-                              or not np.array_equal(o.box_length, self.box_length)):
-            raise ValueError("the route was made by another redistributor (different size, "
-                             "rank or plan)")
+        self._check_owner(route._owner)
+        halo = route.halo
+        if halo is not None and sort_route is not None:
+            raise NotImplementedError("sort_route with a route that holds a halo: unsort, then "
+                                      "reduce_overload, then return_to_source")
         if sort_route is not None:
             _check_sort_route(sort_route)
             if sort_route.n != route.n_local:
                 raise ValueError(f"the sort route has {sort_route.n} rows, the route delivered "
                                  f"{route.n_local}")
         fields, multi = _payload(values, self._dev)
+        n_in = route.n_local + route.n_halo
         for i, f in enumerate(fields):
-            if f.n != route.n_local:
+            if f.n != n_in:
                 raise ValueError(f"values field {i} has {f.n} rows, the route delivered "
-                                 f"{route.n_local}")
+                                 f"{n_in}")
         self.comm.reset_traffic()
         n, stream = route.n_source, _lib.stream_handle()
         rbs = [f.row_bytes for f in fields]
         flats = [f.flat for f in fields]
+        if halo is not None:
+            # the halo part summed onto the first n_local rows (a copy: the
+            # caller's values are not written), which then go home
+            self._check_halo_route(halo)
+            kinds = [_reduce_elem(f, f"values field {i}") for i, f in enumerate(fields)]
+            nl = route.n_local
+            accs = [self._scratch.get(f"halo_red_acc{i}", nl * rb) for i, rb in enumerate(rbs)]
+            for a, t, rb in zip(accs, flats, rbs):
+                a[: nl * rb].copy_(t[: nl * rb])
+            self._reduce_into(halo, accs, [t[nl * rb:] for t, rb in zip(flats, rbs)], kinds)
+            flats = [a[: nl * rb] for a, rb in zip(accs, rbs)]
         if sort_route is not None:   # out of fine-cell order, into the send buffers
             flats = [self._scratch.get(f"unsort{i}", route.n_local * rb)
                      for i, rb in enumerate(rbs)]
@@ -759,7 +823,7 @@ class MPIGridRedistributor:
         return _results(fields, outs, n, multi)
 
     def _redistribute_halo(self, data, position, rows, pos, periodic, overload_lengths,
-                           return_positions):
+                           return_positions, return_route=False):
         """redist.py:157-166 with overload_lengths: the binning kernel also
         writes every row's halo face flags against the cell it lands in
         (mgr_bin_count_halo); rows, flags (a side field of the same pack) and
@@ -799,11 +863,19 @@ class MPIGridRedistributor:
         flags = fsrc[: 2 * m].view(torch.int16) if m else torch.empty(
             0, dtype=torch.int16, device=self._dev)
         op = outs[ip] if rp else None
-        ov_d, ov_p, mo, in_place = exchange_overload(
+        route = None
+        if return_route:   # before the halo: its selections reuse scratch names
+            route = self._take_route()
+            if one:   # the binning's flags stay with the route
+                self._scratch.take("halo_flags_src")
+        ov_d, ov_p, mo, in_place, *hr = exchange_overload(
             self, self.comm, outs[0][: m * rbd], rbd, op[: m * rbp] if rp else None,
             int(position.shape[1]), pos.code, m, list(overload_lengths), periodic=True,
             sel=DeviceSelect(self._dev, self._scratch),
-            arena=(outs[0], op, m, cap), flags=flags, pending=pending)
+            arena=(outs[0], op, m, cap), flags=flags, pending=pending,
+            return_route=return_route)
+        if return_route:
+            route.halo = hr[0]
         if in_place:   # redist.py:166: concatenate(data, overload)
             res_d = outs[0][: (m + mo) * rbd]
             res_p = op[: (m + mo) * rbp] if rp else None
@@ -812,8 +884,8 @@ class MPIGridRedistributor:
             res_p = torch.cat([op[: m * rbp], ov_p]) if rp else None
         res = rows.wrap(res_d, m + mo)
         if rp:
-            return res, fields[ip].wrap(res_p, m + mo)
-        return res
+            res = res, fields[ip].wrap(res_p, m + mo)
+        return (res, route) if return_route else res
 
     def _fine_plan(self, fine_cells):
         fine = np.array(fine_cells).astype(np.int64)
@@ -866,7 +938,7 @@ class MPIGridRedistributor:
         return tuple(res) + (_offsets_like(fields[0].obj, counts, self._dev),)
 
     def exchange_overload_by_position(self, data, position, overload_lengths,
-                                      return_positions=False, periodic=True):
+                                      return_positions=False, periodic=True, return_route=False):
         """redist.py:202-309: the overload (halo) rows of this rank's cell
         from its neighbours; ``data``/``position`` are this rank's local rows
         (already redistributed).  ``return_positions`` (ignored by the
@@ -876,7 +948,11 @@ class MPIGridRedistributor:
         the same selections (one flags pass, one selection count and one pack
         launch per step, one message group per dimension) and come back as a
         tuple in the same order -- what the reference gives called once per
-        field with the same positions."""
+        field with the same positions.  ``return_route``: a HaloRoute for
+        ``reduce_overload`` is appended to the result (it owns the rows' face
+        flags and the selections' workspaces, about 2 * (n_local + n_halo)
+        bytes plus the workspaces, until ``release()``); without it nothing
+        more is allocated, copied or launched."""
         self._check_halo(overload_lengths)
         fields, multi = _payload(data, self._dev)
         self.comm.reset_traffic()
@@ -895,12 +971,93 @@ class MPIGridRedistributor:
             hi, lo = thresholds(self, overload_lengths)
             flags = sel.flags(prow.flat, rows.n, ncols, code, self.dim, hi, lo)
             pflat = None
-        ov_d, ov_p, mo, _ = exchange_overload(
+        ov_d, ov_p, mo, _, *hr = exchange_overload(
             self, self.comm, [f.flat for f in fields] if multi else rows.flat,
             [f.row_bytes for f in fields] if multi else rows.row_bytes, pflat, ncols, code,
-            rows.n, list(overload_lengths), periodic=bool(periodic), sel=sel, flags=flags)
+            rows.n, list(overload_lengths), periodic=bool(periodic), sel=sel, flags=flags,
+            return_route=return_route)
         res = _results(fields, ov_d if multi else [ov_d], mo, multi)
-        return (res, prow.wrap(ov_p, mo)) if return_positions else res
+        if return_positions:
+            res = res, prow.wrap(ov_p, mo)
+        if not return_route:
+            return res
+        return (res + (hr[0],)) if return_positions else (res, hr[0])
+
+    def _check_halo_route(self, halo_route):
+        if not isinstance(halo_route, HaloRoute):
+            raise TypeError("halo_route: a HaloRoute of exchange_overload_by_position(..., "
+                            "return_route=True)")
+        if halo_route.released:
+            raise ValueError("the halo route was released")
+        self._check_owner(halo_route._owner)
+
+    def _check_owner(self, o):
+        if o is not self and (o.size != self.size or o.rank != self.rank
+                              or not np.array_equal(o.grid_topology, self.grid_topology)
+                              or not np.array_equal(o.box_length, self.box_length)):
+            raise ValueError("the route was made by another redistributor (different size, "
+                             "rank or plan)")
+
+    def reduce_overload(self, values, halo_route, local_values=None):
+        """The halo exchange that made ``halo_route``, backwards, with a sum
+        (``exchange_overload_by_position(..., return_route=True)``): ``values``
+        -- one array, or a tuple / list of up to MAX_FIELDS arrays, of
+        ``halo_route.n_halo`` rows each (results computed on the overload
+        rows: force contributions, deposits, neighbour counts ...), float32,
+        float64, int32 or int64 with any trailing shape -- are summed onto the
+        rows they are copies of.  Returns arrays of ``halo_route.n_local``
+        rows in the container of ``values`` (numpy in, numpy out; GPU torch
+        in, GPU torch out): row i is ``local_values[i]`` (same shapes and
+        dtypes as ``values`` with n_local rows; zero when None) plus the
+        values on every overload copy of local row i, anywhere in the world
+        -- the copies of copies in edge and corner regions included.  Neither
+        ``values`` nor ``local_values`` is written.
+
+        Nothing is binned, scanned or counted again and no host sync is
+        needed: per dimension, backwards, one message group with the forward
+        sizes swapped, and one mgr_msel_unpack_add call per field and step
+        (halo.reduce_overload).
+
+        Summation order: a row's contributions are added one at a time in an
+        order fixed by the grid and the rank count, so results are
+        bit-identical from run to run.  For floats they may differ in the
+        last bits between layouts (one rank adds a row's pieces flat, several
+        ranks add them nested, dimension by dimension); integer types and
+        exactly representable sums are identical everywhere."""
+        self._check_halo_route(halo_route)
+        fields, multi = _payload(values, self._dev)
+        for i, f in enumerate(fields):
+            if f.n != halo_route.n_halo:
+                raise ValueError(f"values field {i} has {f.n} rows, the halo route has "
+                                 f"{halo_route.n_halo} overload rows")
+        kinds = [_reduce_elem(f, f"values field {i}") for i, f in enumerate(fields)]
+        n = halo_route.n_local
+        if local_values is None:
+            accs = [torch.zeros(max(n * f.row_bytes, 1), dtype=torch.uint8, device=self._dev)
+                    for f in fields]
+        else:
+            lf, lmulti = _payload(local_values, self._dev)
+            if lmulti != multi or len(lf) != len(fields):
+                raise ValueError("local_values: the same fields as values")
+            accs = []
+            for i, (l_, f) in enumerate(zip(lf, fields)):
+                if l_.n != n:
+                    raise ValueError(f"local_values field {i} has {l_.n} rows, the halo route "
+                                     f"has {n} local rows")
+                if l_.dtype != f.dtype or l_.trailing != f.trailing:
+                    raise ValueError(f"local_values field {i}: dtype and trailing shape of "
+                                     f"values field {i}")
+                a = torch.empty(max(n * f.row_bytes, 1), dtype=torch.uint8, device=self._dev)
+                a[: n * f.row_bytes].copy_(l_.flat[: n * f.row_bytes])
+                accs.append(a)
+        self.comm.reset_traffic()
+        self._reduce_into(halo_route, accs, [f.flat for f in fields], kinds)
+        return _results(fields, accs, n, multi)
+
+    def _reduce_into(self, halo_route, accs, halo_flats, kinds):
+        """accs[f] (flat, n_local rows) += the overload rows' halo_flats[f]."""
+        reduce_overload(self, self.comm, halo_route, accs, halo_flats, [k[0] for k in kinds],
+                        [k[1] for k in kinds], sel=DeviceSelect(self._dev, self._scratch))
 
     def fine_cell_sort(self, data, position, fine_cells, return_positions=False, fine_ids=None,
                        return_route=False):
