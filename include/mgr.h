@@ -494,6 +494,53 @@ int mgr_msel_unpack_add(void* acc, int elem, int ncomp, int64_t n, const uint16_
                         int nsets, const int* masks, int tile_rows, const void* workspace,
                         const void* const* srcs, void* stream);
 
+/* ---------------------------------------------------- ghost-cell lists --
+ * A cell list over a rank's owned rows plus its halo rows, with ghost layers
+ * around the rank's cell (neighbour search, SPH, CIC/TSC deposits).  Both
+ * calls are stream-ordered and neither allocates nor syncs the host.
+ *
+ * mgr_shift_regions: pos is n rows of row_stride elements of pos_dtype
+ * (row_stride >= dim).  The rows are cut into nregions consecutive regions by
+ * region_end (host int64[nregions], non-decreasing, region_end[nregions-1] ==
+ * n; region r = rows [region_end[r-1], region_end[r]), region 0 from row 0; a
+ * region may be empty).  Every row of region r gets, for d < dim,
+ *     pos[row * row_stride + d] = pos[row * row_stride + d] + (T)shift[r * dim + d]
+ * -- one add in the positions' own type T (shift: host double[nregions * dim],
+ * read before the call returns).  A coordinate whose (T)shift is zero is not
+ * stored (its bytes, a -0.0 or a NaN payload included, stay as they were);
+ * columns >= dim are never touched.  The halo exchange calls it on the rows a
+ * periodic wrap brought in (shift = +-box length), so a halo row's position is
+ * the image beside this rank's cell.
+ * MGR_EUNSUPPORTED: pos_dtype other than MGR_F32 / MGR_F64.  MGR_EINVAL: dim
+ * outside 1..MGR_MAX_DIM, n < 0, row_stride < dim, nregions outside 1..64, and
+ * for n > 0 a null pointer, a decreasing region_end or region_end[nregions-1]
+ * != n.  n == 0: MGR_OK, nothing is read.                                   */
+int mgr_shift_regions(void* pos, int pos_dtype, int64_t n, int64_t row_stride, int dim,
+                      int nregions, const int64_t* region_end, const double* shift, void* stream);
+/* mgr_ghost_cells: ids[r] (uint16, device) = the cell of row r in the extended
+ * grid of E_d = fine[d] + 2 * ghost[d] cells per dimension (prod(E) <= 1024,
+ * the bound of the ranked sort mgr_rank_ids + mgr_pack_ranked), numbered
+ * row-major over E with the last axis fastest.  Per coordinate, in float64:
+ *     k = floor(((double)x - origin[d]) / width[d]) + ghost[d]
+ * (the subtract, the divide and the floor each rounded once: numpy's bits).
+ * Rows < n_owned (the rank's own rows) are clamped silently into the interior
+ * [ghost[d], ghost[d] + fine[d] - 1] -- a row that rounds onto its upper face
+ * stays out of the ghost layer.  Rows >= n_owned (halo rows, their positions
+ * unwrapped by mgr_shift_regions) are clamped into [0, E_d - 1]; a NaN takes
+ * the lower bound of its row's range.  When the clamp changed a halo row's k
+ * in some dimension, or a coordinate of it is NaN, the row adds 1 to *outside
+ * (a caller-zeroed device word; NULL: not counted).  origin, width, fine and
+ * ghost are host arrays of dim entries, read before the call returns.  No
+ * histogram is written: mgr_rank_ids / mgr_count_ids read the ids.
+ * MGR_EUNSUPPORTED: pos_dtype other than MGR_F32 / MGR_F64.  MGR_EINVAL: dim
+ * outside 1..MGR_MAX_DIM, n < 0, n_owned outside 0..n, row_stride < dim, and
+ * for n > 0 a null pointer (other than outside), width[d] <= 0 or not finite,
+ * a non-finite origin[d], fine[d] < 1, ghost[d] < 0 or prod(E) > 1024.
+ * n == 0: MGR_OK, nothing is read.                                          */
+int mgr_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned, int64_t row_stride,
+                    int dim, const double* origin, const double* width, const int* fine,
+                    const int* ghost, uint16_t* ids, uint32_t* outside, void* stream);
+
 /* ------------------------------------------------------------ exchange --
  * Replaces comm.alltoall(send_buff) + np.concatenate (redist.py:199):
  * RCCL over xGMI, one process per GPU.  The unique id is made on one rank

@@ -907,6 +907,70 @@ int mgr_halo_flags(const void* pos, int pos_dtype, int64_t n, int64_t row_stride
     return MGR_OK;
 }
 
+// ----------------------------------------------------- ghost-cell lists
+int mgr_shift_regions(void* pos, int pos_dtype, int64_t n, int64_t row_stride, int dim,
+                      int nregions, const int64_t* region_end, const double* shift, void* stream) {
+    if (pos_dtype != MGR_F32 && pos_dtype != MGR_F64)
+        return fail(MGR_EUNSUPPORTED, "shift regions: float32 / float64 positions only (dtype %d)",
+                    pos_dtype);
+    if (dim < 1 || dim > MGR_MAX_DIM) return fail(MGR_EINVAL, "dim %d", dim);
+    if (n < 0) return fail(MGR_EINVAL, "n < 0");
+    if (row_stride < dim) return fail(MGR_EINVAL, "row_stride %lld < dim %d", (long long)row_stride, dim);
+    if (nregions < 1 || nregions > mgr::kMaxRegions)
+        return fail(MGR_EINVAL, "nregions %d not in [1, %d]", nregions, mgr::kMaxRegions);
+    if (n == 0) return MGR_OK;
+    if (!pos || !region_end || !shift) return fail(MGR_EINVAL, "null argument");
+    for (int k = 0; k < nregions; ++k)
+        if (region_end[k] < (k ? region_end[k - 1] : 0))
+            return fail(MGR_EINVAL, "region_end decreases at region %d", k);
+    if (region_end[nregions - 1] != n)
+        return fail(MGR_EINVAL, "region_end ends at %lld, not at n = %lld",
+                    (long long)region_end[nregions - 1], (long long)n);
+    HIP_OK(mgr::launch_shift_regions(pos, pos_dtype, n, row_stride, dim, nregions, region_end,
+                                     shift, (hipStream_t)stream));
+    return MGR_OK;
+}
+
+int mgr_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned, int64_t row_stride,
+                    int dim, const double* origin, const double* width, const int* fine,
+                    const int* ghost, uint16_t* ids, uint32_t* outside, void* stream) {
+    if (pos_dtype != MGR_F32 && pos_dtype != MGR_F64)
+        return fail(MGR_EUNSUPPORTED, "ghost cells: float32 / float64 positions only (dtype %d)",
+                    pos_dtype);
+    if (dim < 1 || dim > MGR_MAX_DIM) return fail(MGR_EINVAL, "dim %d", dim);
+    if (n < 0) return fail(MGR_EINVAL, "n < 0");
+    if (n_owned < 0 || n_owned > n)
+        return fail(MGR_EINVAL, "n_owned %lld not in [0, n = %lld]", (long long)n_owned, (long long)n);
+    if (row_stride < dim) return fail(MGR_EINVAL, "row_stride %lld < dim %d", (long long)row_stride, dim);
+    if (n == 0) return MGR_OK;
+    if (!pos || !origin || !width || !fine || !ghost || !ids) return fail(MGR_EINVAL, "null argument");
+    mgr::GhostGeom g{};
+    int64_t cells = 1;
+    for (int d = 0; d < dim; ++d) {
+        if (!(width[d] > 0.0) || !isfinite(width[d]))
+            return fail(MGR_EINVAL, "width[%d] = %g: positive and finite", d, width[d]);
+        if (!isfinite(origin[d])) return fail(MGR_EINVAL, "origin[%d] = %g: finite", d, origin[d]);
+        if (fine[d] < 1) return fail(MGR_EINVAL, "fine[%d] = %d < 1", d, fine[d]);
+        if (ghost[d] < 0) return fail(MGR_EINVAL, "ghost[%d] = %d < 0", d, ghost[d]);
+        const int64_t e = (int64_t)fine[d] + 2 * (int64_t)ghost[d];
+        if (e > 1024 || (cells *= e) > 1024)
+            return fail(MGR_EINVAL, "extended grid beyond 1024 cells (dimension %d)", d);
+        g.origin[d] = origin[d];
+        g.width[d] = width[d];
+        g.fine[d] = fine[d];
+        g.ghost[d] = ghost[d];
+        g.ext[d] = (int)e;
+    }
+    int off = 1;
+    for (int d = dim - 1; d >= 0; --d) {
+        g.off[d] = off;
+        off *= g.ext[d];
+    }
+    HIP_OK(mgr::launch_ghost_cells(pos, pos_dtype, n, n_owned, row_stride, dim, g, ids, outside,
+                                   (hipStream_t)stream));
+    return MGR_OK;
+}
+
 // ------------------------------------------------------------ exchange
 int mgr_comm_unique_id(void* out_id) {
     if (!out_id) return fail(MGR_EINVAL, "null id");

@@ -78,6 +78,26 @@ struct HaloGeom {
     double ol[MGR_MAX_DIM];
 };
 
+// mgr_shift_regions' table, passed by value: up to kMaxRegions region ends and
+// kShiftVals shift values (region-major, dim per region) per launch.
+constexpr int kMaxRegions = 64;
+constexpr int kShiftVals = 192;
+struct ShiftTable {
+    int64_t end[kMaxRegions];
+    double shift[kShiftVals];
+};
+
+// mgr_ghost_cells' extended grid: ext = fine + 2 * ghost cells per dimension,
+// numbered row-major (off, last axis fastest), prod(ext) <= 1024.
+struct GhostGeom {
+    double origin[MGR_MAX_DIM];
+    double width[MGR_MAX_DIM];
+    int fine[MGR_MAX_DIM];
+    int ghost[MGR_MAX_DIM];
+    int ext[MGR_MAX_DIM];
+    int off[MGR_MAX_DIM];
+};
+
 // Workspace carve for (n, nbins, tile_rows).
 struct Workspace {
     int32_t* counts;     // [nbins][T] destination-major tile histogram
@@ -187,6 +207,14 @@ hipError_t launch_onepass_fields(const Geom& g, const FineGeom* fg, int nf, void
                                  void* workspace, hipStream_t s);
 hipError_t launch_halo_flags(const void* pos, int pos_dtype, int64_t n, int64_t stride, int dim,
                              const double* hi, const double* lo, uint16_t* flags, hipStream_t s);
+// Ghost-cell lists (mgr_ghost.hip): pos_dtype MGR_F32 or MGR_F64, arguments
+// validated by the caller.
+hipError_t launch_shift_regions(void* pos, int pos_dtype, int64_t n, int64_t stride, int dim,
+                                int nregions, const int64_t* region_end, const double* shift,
+                                hipStream_t s);
+hipError_t launch_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned,
+                              int64_t stride, int dim, const GhostGeom& g, uint16_t* ids,
+                              uint32_t* outside, hipStream_t s);
 
 // Test hooks (include/mgr_instrument.h, mgr_test_hook): switches that make a
 // product-reachable fallback or shape run on inputs that would not take it,

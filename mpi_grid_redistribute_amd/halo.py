@@ -15,7 +15,8 @@ that lie within ``overload_lengths[d]`` of the shared face:
 Data and positions travel with the same selections (the reference sends
 them as two passes, :264); rows received in earlier dimensions are forwarded
 in later ones, which fills the edge/corner regions.  Kept reference quirks:
-positions are not shifted across the periodic boundary; with
+positions are not shifted across the periodic boundary (``unwrap=True``
+shifts them: exchange_overload, mgr_shift_regions); with
 ``periodic=False`` the left send uses the right neighbour's flag (:287);
 ``redistribute_by_position`` never forwards ``periodic`` (:165).
 
@@ -161,19 +162,53 @@ class HaloRoute:
         self._live = False
 
 
+def shift_regions(pos_flat, code, ncols, dim, ends, shifts):
+    """mgr_shift_regions on the rows at the start of ``pos_flat`` (a flat uint8
+    view of (rows, ncols) positions of dtype ``code``): region r = rows
+    [ends[r-1], ends[r]) gets += shifts[r] (dim values), in chunks of 64
+    regions (the call's limit)."""
+    ends = [int(e) for e in ends]
+    for k0 in range(0, len(ends), 64):
+        k1 = min(len(ends), k0 + 64)
+        r0 = ends[k0 - 1] if k0 else 0
+        n = ends[k1 - 1] - r0
+        if n <= 0 or not any(any(s) for s in shifts[k0:k1]):
+            continue
+        e = (ctypes.c_int64 * (k1 - k0))(*[x - r0 for x in ends[k0:k1]])
+        s = (ctypes.c_double * ((k1 - k0) * dim))(*[float(v) for row in shifts[k0:k1]
+                                                    for v in row])
+        _lib.call("mgr_shift_regions",
+                  ctypes.c_void_p(pos_flat.data_ptr() + r0 * ncols * _lib.POS_ITEMSIZE[code]),
+                  code, n, ncols, dim, k1 - k0, e, s, _lib.stream_handle())
+
+
 def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, pending=(),
-               multi=False, owner=None):
+               multi=False, owner=None, unwrap=None):
     """exchange_overload when every neighbour is this rank: all pieces are
     known from the local rows' flags, so one selection pass counts them all
     and one multi-set pack writes every row straight to each of its pieces
     in the store -- the local rows are read once, not once per dimension,
     and nothing is staged or received.  ``srcs`` / ``rbs``: the payload's
     fields, then the positions when carried; ``multi``: the payload is a list
-    of fields (arena[0] a list of stores, the data returned as a list)."""
+    of fields (arena[0] a list of stores, the data returned as a list).
+    ``unwrap``: (position dtype code, position columns, box lengths) -- the
+    carried positions of every piece are shifted to the image beside the cell
+    (mask bit 2d: beyond the right face, the copy lies on the left, -L_d; bit
+    2d+1: +L_d), one mgr_shift_regions call once the piece sizes are known."""
     pieces = self_halo_pieces(dim)
     h, cnt = sel.msel_masks(flags, n, pieces, "_self")
     F = len(rbs)
     D = F - 1 if carry_pos else F                         # payload fields
+
+    def unwrapped(out, offs):
+        """out: the fields' overload rows, the pieces ending at offs[1:]."""
+        if unwrap is not None:
+            code, ncols, box = unwrap
+            shifts = [[(-box[d] if m >> (2 * d) & 1 else 0.0) + (box[d] if m >> (2 * d + 1) & 1
+                                                                  else 0.0)
+                       for d in range(dim)] for m in pieces]
+            shift_regions(out[D], code, ncols, dim, offs[1:], shifts)
+        return out
 
     def stores():
         return (list(arena[0]) if multi else [arena[0]]) + ([arena[1]] if carry_pos else [])
@@ -205,26 +240,27 @@ def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, 
         check_counts(c, [])
     _agree_counts(transport, counts, [])
     total = int(counts.sum())
+    offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     if placed and total <= arena[3]:
         _lib.alg_add("halo_pack", 2 * n + 2 * total * sum(rbs))
         if not total:
             return nothing(True)
         b = arena[2]
-        return result([ast[f][b * rbs[f]:(b + total) * rbs[f]] for f in range(F)], total, True)
+        return result(unwrapped([ast[f][b * rbs[f]:(b + total) * rbs[f]] for f in range(F)],
+                                offs), total, True)
     if arena is not None and total <= arena[3]:
         st, base, in_arena = stores(), arena[2], True
     else:
         st = [torch.empty(max(total, 1) * rb, dtype=torch.uint8, device=dev) for rb in rbs]
         base, in_arena = 0, False
-    offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     dsts = [[st[f][(base + int(offs[k])) * rbs[f]:(base + int(offs[k + 1])) * rbs[f]]
              if counts[k] else None for k in range(len(pieces))] for f in range(F)]
     if total:
         sel.msel_pack_fields(h, srcs, rbs, dsts, total)
     if not total:
         return nothing(in_arena)
-    return result([st[f][base * rbs[f]:(base + total) * rbs[f]] for f in range(F)], total,
-                  in_arena)
+    return result(unwrapped([st[f][base * rbs[f]:(base + total) * rbs[f]] for f in range(F)],
+                            offs), total, in_arena)
 
 
 def neighbours(R, d, periodic):
@@ -376,7 +412,7 @@ class DeviceSelect:
 
 def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n,
                       overload_lengths, periodic=True, sel=None, arena=None, flags=None,
-                      pending=(), return_route=False):
+                      pending=(), return_route=False, unwrap=False):
     """Overload rows of rank R (redist.py:202-309).  ``data_flat``: flat uint8
     tensor of this rank's n payload rows of ``rbd`` bytes; ``pos_flat``: their
     positions (n, ncols) rows of any position dtype (ncols >= dim), or None when the
@@ -400,8 +436,30 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
 
     ``return_route``: a HaloRoute for ``reduce_overload`` is appended to the
     result; every dimension's buffer selection then keeps a workspace of its
-    own.  Without it the call allocates, copies and launches nothing more."""
+    own.  Without it the call allocates, copies and launches nothing more.
+
+    ``unwrap``: the carried positions of the overload rows come back as the
+    periodic image beside this rank's cell instead of the owner's coordinates
+    (which image a copy is, is known only here: a grid extent of 1, or of 2
+    with 2 * ol > cell, delivers the same row as a left and a right copy with
+    identical position and flags).  General path: once dimension d's receives
+    are posted, one mgr_shift_regions call on the rows just appended -- the
+    rows from a get + box_length[d] on the last cell of the dimension, the
+    rows from b get - box_length[d] on the first, a self dimension both --
+    and later dimensions forward the shifted positions (their selections read
+    the stored flags only).  One-rank path: one call over the pieces
+    (_self_halo).  With ``periodic=False`` nothing is shifted.  Needs carried
+    positions (ValueError) of float32 or float64 (TypeError); data rows,
+    counts, order and the route are what ``unwrap=False`` gives, which
+    launches nothing new."""
     dim = R.dim
+    if unwrap:
+        if pos_flat is None:
+            raise ValueError("unwrap=True needs the positions carried (return_positions=True)")
+        if pos_code not in (_lib.MGR_F32, _lib.MGR_F64):
+            raise TypeError("unwrap=True: float32 or float64 positions (a shifted float16, "
+                            "integer or bool position is not the row's image)")
+    box = [float(x) for x in R.box_length] if unwrap else None
     assert len(overload_lengths) == dim, \
         "Overload lengths must be the same length as the dimensions"  # redist.py:245
     multi = isinstance(data_flat, (list, tuple))
@@ -437,7 +495,8 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     selfd = [a == me and b == me for a, b, _, _ in nb]
     if dim <= 3 and all(selfd) and all(ka and kb for _, _, ka, kb in nb):
         return _self_halo(transport, sel, srcs[:F - 1], rbs[:F - 1], flags, n, dim, carry_pos,
-                          arena, dev, pending, multi, R if return_route else None)
+                          arena, dev, pending, multi, R if return_route else None,
+                          (pos_code, ncols, box) if unwrap else None)
     for c in pending:   # (the general path reads them here)
         check_counts(c.cpu().numpy(), [])
 
@@ -534,6 +593,19 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
         if any(t is not None for t in dsts[0]):
             sel.msel_pack_fields(lh, srcs, rbs, dsts, sum(sum(local_pieces(d)) for d in dims))
 
+    def unwrap_dim(d, ia, ib, new_m):
+        """The rows dimension d appended, shifted to the image beside this
+        cell: [ia, ib) came from a (+L on the last cell), [ib, new_m) from b
+        (-L on the first)."""
+        if not (unwrap and periodic) or new_m == ia:
+            return
+        up = box[d] if int(R.rank_cell_index[d]) == int(R.grid_topology[d]) - 1 else 0.0
+        down = -box[d] if int(R.rank_cell_index[d]) == 0 else 0.0
+        if up or down:
+            e = [0.0] * dim
+            shift_regions(store(D, ia, new_m - ia), pos_code, ncols, dim, [ib - ia, new_m - ia],
+                          [e[:d] + [up] + e[d + 1:], e[:d] + [down] + e[d + 1:]])
+
     first = [d for d in range(dim) if not selfd[d] or d == 0]
     if selfd[0]:
         nla, nlb = local_pieces(0)
@@ -595,6 +667,7 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
                        gbuf[f][nga * rbs[f]:gsz * rbs[f]] if ngb else None] for f in range(F)]
             sel.msel_pack_fields(gh, [store(f, 0, m) for f in range(F)], rbs, gd, gsz)
         if selfd[d]:
+            unwrap_dim(d, ia, ib, new_m)
             m = new_m
             continue
         ops = []
@@ -615,6 +688,7 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
                 if rg_:
                     ops.append(("recv", frm, store(f, at + rl_, rg_)))
         _p2p(transport, ops)
+        unwrap_dim(d, ia, ib, new_m)
         m = new_m
     # one agreement per call: every rank raises together if any scan failed
     if transport.any_failed(failed):

@@ -317,6 +317,53 @@ def _offsets_like(data, counts, dev):
     return offsets.cpu() if isinstance(data, torch.Tensor) else offsets.cpu().numpy()
 
 
+GHOST_MAX_CELLS = 1024   # the ranked sort's bound (mgr_rank_ids + mgr_pack_ranked)
+
+
+def ghost_grid(cell_length, cell_limits, fine_cells, overload_lengths):
+    """The extended fine grid of a rank's cell with ghost layers -- the single
+    definition ``MPIGridRedistributor.ghost_grid`` / ``ghost_cell_sort`` and
+    mgr_ghost_cells share (host numpy, no GPU).  ``cell_length[d]`` and
+    ``cell_limits[d] = (low, high)`` describe the cell.  Returns (ghost,
+    extents, origin, width):
+
+      width[d]   = cell_length[d] / fine_cells[d]              (float64)
+      ghost[d]   = ceil(overload_lengths[d] / width[d]), 0 for a zero length
+      extents[d] = fine_cells[d] + 2 * ghost[d]
+      origin[d]  = cell_limits[d, 0]
+
+    Cell k of dimension d covers [origin + (k - ghost) * width, origin + (k -
+    ghost + 1) * width); cells ghost .. ghost + fine - 1 are the rank's own.
+    ValueError: prod(extents) beyond 1024 cells, a fine cell count < 1, a
+    negative or non-finite overload length."""
+    cl = np.asarray(cell_length, dtype=np.float64)
+    fine = np.array(fine_cells).astype(np.int64)
+    ol = np.asarray(overload_lengths, dtype=np.float64)
+    dim = len(cl)
+    if fine.ndim != 1 or len(fine) != dim or ol.ndim != 1 or len(ol) != dim:
+        raise ValueError(f"fine_cells and overload_lengths must have {dim} entries")
+    if (fine < 1).any():
+        raise ValueError(f"fine_cells {fine.tolist()}: at least 1 per dimension")
+    if not np.isfinite(ol).all() or (ol < 0).any():
+        raise ValueError(f"overload_lengths {ol.tolist()}: finite and >= 0")
+    width = cl / fine
+    if not np.isfinite(width).all() or (width <= 0).any():
+        raise ValueError(f"cell lengths {cl.tolist()}: positive and finite")
+    ghost = np.where(ol == 0, 0.0, np.ceil(ol / width))
+    if (ghost > GHOST_MAX_CELLS).any():
+        raise ValueError(f"ghost layers of {ghost.tolist()} cells: beyond {GHOST_MAX_CELLS}")
+    ghost = ghost.astype(np.int64)
+    extents = fine + 2 * ghost
+    cells = 1
+    for e in extents:
+        cells *= int(e)
+    if cells > GHOST_MAX_CELLS:
+        raise ValueError(f"extended grid {extents.tolist()} has {cells} cells: at "
+                         f"most {GHOST_MAX_CELLS} (the ranked sort's bound); use fewer fine cells")
+    origin = np.ascontiguousarray(np.asarray(cell_limits, dtype=np.float64)[:, 0])
+    return ghost, extents, origin, width
+
+
 def _fine_sort(plan, coarse, dim, dev, data, position, return_positions, fine_ids=None,
                return_route=False):
     """The fine cells of the rows -- ``fine_ids`` as given (computed at the
@@ -639,7 +686,12 @@ class MPIGridRedistributor:
         of the plain result, computed from fine cells binned at the source.
         ``return_positions``: (data, positions) -- (data, [positions,]
         offsets) with ``fine_cells``; ``data`` is the tuple of fields for a
-        SoA payload.  ``return_route``: (result, route) -- ``result`` is what
+        SoA payload.  ``overload_lengths`` together with ``fine_cells`` (one
+        array, float32 / float64 positions): the ghost cell list -- the
+        received rows and their halo rows, the halo positions unwrapped,
+        sorted over the extended grid: what ``ghost_cell_sort`` returns for
+        them, (data, [positions,] offsets[prod(extents) + 1]).
+        ``return_route``: (result, route) -- ``result`` is what
         the call returns otherwise, ``route`` a Route for ``return_to_source``
         (rows of any dtype go back one to one).  Not with ``overload_lengths``:
         halo rows are copies and their return is a reduction, a different
@@ -681,9 +733,27 @@ class MPIGridRedistributor:
         n = fields[0].n
         if pos.n != n:
             raise ValueError(f"data has {n} rows, position has {pos.n}")
+        if fine_cells is not None and overload_lengths is not None:
+            # the ghost cell list: owned + halo rows, halo positions unwrapped,
+            # sorted over the extended grid
+            if multi:
+                raise NotImplementedError(
+                    "overload_lengths and fine_cells with a SoA (tuple) payload in one call: "
+                    "redistribute_by_position(fields, pos, return_positions=True), then "
+                    "exchange_overload_by_position(fields, local_pos, overload_lengths, "
+                    "return_positions=True, unwrap=True), then ghost_cell_sort on the "
+                    "concatenated fields")
+            self._check_halo(overload_lengths)
+            if pos.code not in _TORCH_POS:
+                raise TypeError("overload_lengths with fine_cells: float32 or float64 positions")
+            self.ghost_grid(fine_cells, overload_lengths)   # refuse a grid too large up front
+            info = {}
+            both, both_pos = self._redistribute_halo(data, position, fields[0], pos, periodic,
+                                                     overload_lengths, True, unwrap=True,
+                                                     info=info)
+            return self.ghost_cell_sort(both, both_pos, info["n_local"], fine_cells,
+                                        overload_lengths, return_positions=return_positions)
         if fine_cells is not None:
-            if overload_lengths is not None:
-                raise NotImplementedError("fine_cells together with overload_lengths")
             return self._redistribute_fine(data, position, fields, multi, pos, periodic,
                                            fine_cells, return_positions)
         halo = overload_lengths is not None
@@ -823,14 +893,17 @@ class MPIGridRedistributor:
         return _results(fields, outs, n, multi)
 
     def _redistribute_halo(self, data, position, rows, pos, periodic, overload_lengths,
-                           return_positions, return_route=False):
+                           return_positions, return_route=False, unwrap=False, info=None):
         """redist.py:157-166 with overload_lengths: the binning kernel also
         writes every row's halo face flags against the cell it lands in
         (mgr_bin_count_halo); rows, flags (a side field of the same pack) and
         wrapped positions (:164) are redistributed together; the overload
         exchange (halo.py) then starts from the received flags and appends
         the halo rows in place after the m received rows while they fit the
-        spare capacity (no concatenation copies)."""
+        spare capacity (no concatenation copies).  ``unwrap``: the halo rows'
+        positions come back unwrapped (halo.exchange_overload); ``info``: a
+        dict that receives ``n_local``, the redistributed rows before the
+        halo's."""
         flags_src = self._scratch.get("halo_flags_src", max(rows.n, 1) * 2)
         rp = bool(return_positions)
         # one rank: the rows keep their order (one bin, nothing dropped), so the
@@ -873,9 +946,11 @@ class MPIGridRedistributor:
             int(position.shape[1]), pos.code, m, list(overload_lengths), periodic=True,
             sel=DeviceSelect(self._dev, self._scratch),
             arena=(outs[0], op, m, cap), flags=flags, pending=pending,
-            return_route=return_route)
+            return_route=return_route, unwrap=unwrap)
         if return_route:
             route.halo = hr[0]
+        if info is not None:
+            info["n_local"] = m
         if in_place:   # redist.py:166: concatenate(data, overload)
             res_d = outs[0][: (m + mo) * rbd]
             res_p = op[: (m + mo) * rbp] if rp else None
@@ -938,7 +1013,8 @@ class MPIGridRedistributor:
         return tuple(res) + (_offsets_like(fields[0].obj, counts, self._dev),)
 
     def exchange_overload_by_position(self, data, position, overload_lengths,
-                                      return_positions=False, periodic=True, return_route=False):
+                                      return_positions=False, periodic=True, return_route=False,
+                                      unwrap=False):
         """redist.py:202-309: the overload (halo) rows of this rank's cell
         from its neighbours; ``data``/``position`` are this rank's local rows
         (already redistributed).  ``return_positions`` (ignored by the
@@ -952,8 +1028,17 @@ class MPIGridRedistributor:
         ``reduce_overload`` is appended to the result (it owns the rows' face
         flags and the selections' workspaces, about 2 * (n_local + n_halo)
         bytes plus the workspaces, until ``release()``); without it nothing
-        more is allocated, copied or launched."""
+        more is allocated, copied or launched.  ``unwrap`` (with
+        ``return_positions``; float32 / float64 positions): the returned
+        positions of the overload rows are the periodic images beside this
+        rank's cell -- a row that came across the box boundary reads x + L or
+        x - L, so a left and a right copy of the same row differ -- instead of
+        the owners' coordinates (the reference's); what ``ghost_cell_sort``
+        takes.  The data rows, their count and order do not change."""
         self._check_halo(overload_lengths)
+        if unwrap and not return_positions:
+            raise ValueError("unwrap=True needs return_positions=True (the positions are what "
+                             "it changes)")
         fields, multi = _payload(data, self._dev)
         self.comm.reset_traffic()
         rows = fields[0]
@@ -975,7 +1060,7 @@ class MPIGridRedistributor:
             self, self.comm, [f.flat for f in fields] if multi else rows.flat,
             [f.row_bytes for f in fields] if multi else rows.row_bytes, pflat, ncols, code,
             rows.n, list(overload_lengths), periodic=bool(periodic), sel=sel, flags=flags,
-            return_route=return_route)
+            return_route=return_route, unwrap=bool(unwrap))
         res = _results(fields, ov_d if multi else [ov_d], mo, multi)
         if return_positions:
             res = res, prow.wrap(ov_p, mo)
@@ -1081,6 +1166,81 @@ class MPIGridRedistributor:
         plan = self._fine_plan(fine_cells)
         return _fine_sort(plan, self._plan, self.dim, self._dev, data, position,
                           return_positions, fine_ids, return_route)
+
+    def ghost_grid(self, fine_cells, overload_lengths):
+        """(ghost, extents, origin, width) of this rank's extended fine grid
+        (host numpy; the module's ``ghost_grid`` on this rank's cell): width =
+        cell_length / fine_cells, ghost[d] = ceil(overload_lengths[d] /
+        width[d]) layers on either side, extents = fine_cells + 2 * ghost,
+        origin = the cell's lower corner.  ValueError beyond 1024 cells."""
+        return ghost_grid(self.cell_length, self.rank_cell_limits, fine_cells, overload_lengths)
+
+    def ghost_cell_sort(self, data, position, n_local, fine_cells, overload_lengths,
+                        return_positions=False, return_route=False):
+        """The cell list a neighbour search, an SPH step or a CIC/TSC deposit
+        needs: this rank's owned rows AND its halo rows, stably sorted over the
+        extended grid of ``ghost_grid(fine_cells, overload_lengths)`` -- the
+        rank's fine cells with ghost layers around them.  ``data``: one array
+        or a SoA tuple / list of ``n_local + n_halo`` rows, the layout the halo
+        calls return (owned rows first; the two-call form: concatenate the
+        redistributed rows and the overload rows per field); ``position``
+        ((N, >= dim) float32 / float64): their positions, the halo rows'
+        unwrapped (``exchange_overload_by_position(..., unwrap=True)``).
+        Returns (sorted data, offsets[prod(extents) + 1]) -- (data, positions,
+        offsets) with ``return_positions`` -- in the containers of the inputs,
+        plus a SortRoute with ``return_route`` (``unsort`` brings per-row
+        results back to the n_local + n_halo layout, where ``reduce_overload``
+        takes them).  Cell ids are row-major over ``extents``, last axis
+        fastest; the block [ghost, ghost + fine) in every dimension holds
+        exactly the owned rows (an owned row that rounds onto a face of the
+        cell is clamped into it), the layers around it only halo rows.  A halo
+        row beyond the ghost layers (a position that was not unwrapped, a NaN)
+        is counted on the device and turns the offsets' counts to -1: host
+        results raise, as after a failed scan.  One mgr_ghost_cells launch,
+        then the ranked sort of fine_cell_sort (_sort_by_ids), unchanged."""
+        ghost, ext, origin, width = self.ghost_grid(fine_cells, overload_lengths)
+        dev = self._dev
+        rows, multi = _payload(data, dev)
+        pos = Positions(position, self.dim, dev, data_rows=_alias_rows(position, rows))
+        if pos.code not in _TORCH_POS:
+            raise TypeError("ghost_cell_sort: float32 or float64 positions")
+        n = rows[0].n
+        if pos.n != n:
+            raise ValueError(f"data has {n} rows, position has {pos.n}")
+        n_local = int(n_local)
+        if not 0 <= n_local <= n:
+            raise ValueError(f"n_local {n_local} outside 0..{n}")
+        nb = int(np.prod(ext))
+        prow = Rows(position, dev) if return_positions else None
+        fields = rows + ([prow] if prow else [])
+        ids = torch.empty(max(n, 1), dtype=torch.int16, device=dev)
+        outside = torch.zeros(1, dtype=torch.int32, device=dev)
+        fine = np.array(fine_cells).astype(np.int64)
+        _lib.call("mgr_ghost_cells", ctypes.c_void_p(pos.addr), pos.code, n, n_local, pos.stride,
+                  self.dim, origin.ctypes.data_as(ctypes.c_void_p),
+                  width.ctypes.data_as(ctypes.c_void_p),
+                  (ctypes.c_int * self.dim)(*[int(x) for x in fine]),
+                  (ctypes.c_int * self.dim)(*[int(x) for x in ghost]), _lib.ptr(ids),
+                  _lib.ptr(outside), _lib.stream_handle())
+        ids = ids[:n]
+        sroute = None
+        if return_route:
+            outs, counts, sroute = _sort_by_ids(fields, ids, n, nb, dev, check_ids=False,
+                                                route=True)
+        else:
+            outs, counts = _sort_by_ids(fields, ids, n, nb, dev, check_ids=False)
+        counts.masked_fill_(outside.ne(0), -1)   # read with the offsets: no sync of its own
+        nd = len(rows)
+        res = [_results(rows, outs[:nd], n, multi)]
+        if prow:
+            res.append(prow.wrap(outs[nd], n))
+        try:
+            res.append(_offsets_like(rows[0].obj, counts, dev))
+        except _lib.MgrError as e:
+            raise _lib.MgrError("ghost_cell_sort: a halo row lies beyond the ghost layers (a "
+                                "position that was not unwrapped or is NaN, or overload_lengths "
+                                f"smaller than the halo's), or: {e}") from None
+        return tuple(res) + ((sroute,) if return_route else ())
 
     def get_cell_number_from_indexes_host(self, indexes, periodic=True):
         """redist.py:73-85 on the host (neighbour ranks of the halo exchange)."""
