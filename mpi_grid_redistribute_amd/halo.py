@@ -58,6 +58,7 @@ call (the wide kernel from 4 fields on, mgr.h).
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -103,6 +104,40 @@ def _agree_counts(transport, sent, received):
         check_counts([-1], [])     # a peer failed: raise here too
 
 
+def _swap_counts(transport, sel, dev, counts, nbs, failed):
+    """One count swap with the neighbours ``nbs`` (neighbour tuples, one per
+    dimension concerned): ``counts`` = device int64, per dimension the rows to
+    a and to b (None: nothing selected, zeros).  One group of 8-byte messages,
+    one host read.  Returns the sizes sent, the sizes received ([from_b,
+    from_a] per dimension) and the new ``failed``: a failed selection scan
+    (here, or at a neighbour through its messages) travels as the failure bit
+    and is announced on from then on, so the neighbours' neighbours learn too;
+    sizes stay as announced (the neighbours post receives of them) and the
+    ranks agree at the end of the exchange.  A side that does not send: 0."""
+    k = 2 * len(nbs)
+    send = torch.zeros(k, dtype=torch.int64, device=dev)
+    recv = torch.zeros(k, dtype=torch.int64, device=dev)
+    if counts is not None:
+        send.copy_(_encode_counts(counts))
+    if failed:
+        send.fill_(_FAIL)
+    ops = []
+    for i, (a, b, keep_a, keep_b) in enumerate(nbs):
+        if not keep_a:
+            send[2 * i].zero_()
+        if not keep_b:
+            send[2 * i + 1].zero_()
+        ops += [("send", a, send[2 * i:2 * i + 1].view(torch.uint8)),
+                ("recv", b, recv[2 * i:2 * i + 1].view(torch.uint8)),
+                ("send", b, send[2 * i + 1:2 * i + 2].view(torch.uint8)),
+                ("recv", a, recv[2 * i + 1:2 * i + 2].view(torch.uint8))]
+    _p2p(transport, ops)
+    sent, received = sel.to_host([send, recv])
+    sent, f1 = _decode(sent)
+    received, f2 = _decode(received)
+    return sent, received, failed or f1 or f2
+
+
 def self_halo_pieces(dim):
     """The overload rows of a rank that is its own neighbour in every
     dimension (one rank; periodic), as pieces in store order: piece = the
@@ -121,6 +156,65 @@ def self_halo_pieces(dim):
     return buf
 
 
+class Step(namedtuple("Step", "nla nlb nga ngb rla rga rlb rgb ia ib m gh")):
+    """One dimension's step of the general path, as the host knows it once
+    the counts are read: ``nla, nlb, nga, ngb`` rows sent (local / buffer
+    piece, to a / b), ``rla, rga, rlb, rgb`` rows received (the senders' local
+    / buffer pieces, from a / b), ``ia, ib`` where the received pieces are
+    appended -- concat(buffer, from_a, from_b), redist.py:305 --, ``m`` the
+    buffer rows before the dimension and ``gh`` the buffer's selection handle
+    (None: nothing was selected)."""
+    __slots__ = ()
+    to_a = property(lambda s: s.nla + s.nga)
+    to_b = property(lambda s: s.nlb + s.ngb)
+    from_a = property(lambda s: s.rla + s.rga)
+    from_b = property(lambda s: s.rlb + s.rgb)
+    end = property(lambda s: s.m + s.from_a + s.from_b)    # buffer rows after the dimension
+
+
+def _forward_group(s, d, a, b, store, local, gbuf):
+    """Dimension d's message group towards other ranks, in the reference's
+    order: step 1 (send to a, receive from b) then step 2, and inside a step
+    per field: local send, buffer send, local receive, buffer receive (RCCL
+    matches a pair's messages in posting order).  ``local``: the _LocalSends
+    holding the packed local pieces; ``gbuf[f]``: field f's packed buffer
+    pieces, to a then to b; the receives land appended in ``store``."""
+    ops = []
+    for side, (to, frm, nl, ng, go, rl, rg, at) in enumerate(
+            ((a, b, s.nla, s.nga, 0, s.rlb, s.rgb, s.ib),
+             (b, a, s.nlb, s.ngb, s.nga, s.rla, s.rga, s.ia))):
+        for f, rb in enumerate(store.rbs):
+            if nl:
+                ops.append(("send", to, local.staged(d, f, side)))
+            if ng:
+                ops.append(("send", to, gbuf[f][go * rb:(go + ng) * rb]))
+            if rl:
+                ops.append(("recv", frm, store.rows(f, at, rl)))
+            if rg:
+                ops.append(("recv", frm, store.rows(f, at + rl, rg)))
+    return ops
+
+
+def _backward_group(s, a, b, S, stage, ebs):
+    """_forward_group with sender and receiver swapped (reduce_overload): the
+    rows received from b / a go back from the value stores ``S`` -- they are
+    contiguous there, nothing is packed -- and the values for this rank's own
+    sends arrive in ``stage``, to_a's then to_b's.  Towards a pair of ranks
+    the sends and the receives match in posting order (a == b on a grid
+    extent of 2)."""
+    ops = []
+    for f, eb in enumerate(ebs):
+        if s.from_b:
+            ops.append(("send", b, S[f][s.ib * eb:(s.ib + s.from_b) * eb]))
+        if s.to_a:
+            ops.append(("recv", a, stage[f][: s.to_a * eb]))
+        if s.from_a:
+            ops.append(("send", a, S[f][s.ia * eb:(s.ia + s.from_a) * eb]))
+        if s.to_b:
+            ops.append(("recv", b, stage[f][s.to_a * eb:(s.to_a + s.to_b) * eb]))
+    return ops
+
+
 class HaloRoute:
     """What ``reduce_overload`` needs to sum per-row results on overload rows
     back onto the rows they are copies of (``exchange_overload(...,
@@ -129,11 +223,9 @@ class HaloRoute:
 
       * the local rows' face flags (2 B/row) and their selection handle (masks
         and the msel workspace as mgr_scan left it);
-      * per dimension: the buffer's selection handle (its own workspace, the
-        flags of the rows received so far), the neighbours, and the host-side
-        sizes ``nla, nlb, nga, ngb`` (sent: local / buffer piece to a / b),
-        ``rla, rga, rlb, rgb`` (received), ``ia, ib`` (where the received
-        pieces were appended) and ``m`` (buffer rows before the dimension);
+      * per dimension: the neighbours and the ``Step`` -- the host-side sizes
+        and places, and the buffer's selection handle (its own workspace, the
+        flags of the rows received so far);
       * on the one-rank path the one selection handle over the 3^dim - 1
         pieces and the piece sizes.
 
@@ -182,6 +274,28 @@ def shift_regions(pos_flat, code, ncols, dim, ends, shifts):
                   code, n, ncols, dim, k1 - k0, e, s, _lib.stream_handle())
 
 
+def _arena_stores(arena, multi, carry_pos):
+    """The arena's stores in field order: payload, then positions when carried."""
+    return (list(arena[0]) if multi else [arena[0]]) + ([arena[1]] if carry_pos else [])
+
+
+def _result(sel, dev, shape, out, rows, in_arena, route=None):
+    """What exchange_overload returns.  ``shape``: (payload fields, whether
+    the payload is a list, whether positions are carried); ``out``: the
+    fields' overload rows, payload then positions (not read when there are no
+    rows); ``route``: None, or (the msel workspaces the route takes out of the
+    scratch, HaloRoute's arguments but n_halo)."""
+    D, multi, carry_pos = shape
+    if not rows:
+        out = [torch.empty(0, dtype=torch.uint8, device=dev)] * (D + carry_pos)
+    res = (out[:D] if multi else out[0]), (out[D] if carry_pos else None), rows, in_arena
+    if route is None:
+        return res
+    for name in route[0]:
+        sel.take(name)   # the route owns the workspaces from here on
+    return res + (HaloRoute(n_halo=rows, **route[1]),)
+
+
 def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, pending=(),
                multi=False, owner=None, unwrap=None):
     """exchange_overload when every neighbour is this rank: all pieces are
@@ -210,28 +324,18 @@ def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, 
             shift_regions(out[D], code, ncols, dim, offs[1:], shifts)
         return out
 
-    def stores():
-        return (list(arena[0]) if multi else [arena[0]]) + ([arena[1]] if carry_pos else [])
-
     def result(out, total, in_arena):
-        data = out[:D] if multi else out[0]
-        res = data, (out[D] if carry_pos else None), total, in_arena
-        if owner is None:
-            return res
-        sel.take("msel_ws_self")   # the route owns the workspace from here on
-        return res + (HaloRoute(owner, n, total, flags, self_handle=h,
-                                self_counts=np.asarray(counts, dtype=np.int64).copy()),)
-
-    def nothing(in_arena):
-        empty = torch.empty(0, dtype=torch.uint8, device=dev)
-        return result([empty] * F, 0, in_arena)
+        route = None if owner is None else (["msel_ws_self"], dict(
+            owner=owner, n_local=n, flags=flags, self_handle=h,
+            self_counts=np.asarray(counts, dtype=np.int64).copy()))
+        return _result(sel, dev, (D, multi, carry_pos), out, total, in_arena, route)
     placed = arena is not None and arena[3] > 0
     # the one host read is enqueued BEFORE the placed pack and waited for on
     # its own event: the host finishes this call (and launches the caller's
     # next work) while the pack runs, instead of idling the GPU after it
     read = sel.to_host_start([cnt] + list(pending))
     if placed:   # into the arena before the sizes are known: no gap at the sync
-        ast = stores()
+        ast = _arena_stores(arena, multi, carry_pos)
         sel.msel_pack_placed(h, srcs, rbs, [ast[f][arena[2] * rbs[f]:] for f in range(F)],
                              arena[3])
     got = sel.to_host_wait(read)                          # the one host sync
@@ -244,12 +348,12 @@ def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, 
     if placed and total <= arena[3]:
         _lib.alg_add("halo_pack", 2 * n + 2 * total * sum(rbs))
         if not total:
-            return nothing(True)
+            return result(None, 0, True)
         b = arena[2]
         return result(unwrapped([ast[f][b * rbs[f]:(b + total) * rbs[f]] for f in range(F)],
                                 offs), total, True)
     if arena is not None and total <= arena[3]:
-        st, base, in_arena = stores(), arena[2], True
+        st, base, in_arena = _arena_stores(arena, multi, carry_pos), arena[2], True
     else:
         st = [torch.empty(max(total, 1) * rb, dtype=torch.uint8, device=dev) for rb in rbs]
         base, in_arena = 0, False
@@ -258,7 +362,7 @@ def _self_halo(transport, sel, srcs, rbs, flags, n, dim, carry_pos, arena, dev, 
     if total:
         sel.msel_pack_fields(h, srcs, rbs, dsts, total)
     if not total:
-        return nothing(in_arena)
+        return result(None, 0, in_arena)
     return result(unwrapped([st[f][base * rbs[f]:(base + total) * rbs[f]] for f in range(F)],
                             offs), total, in_arena)
 
@@ -307,6 +411,26 @@ def halo_capacity(R, m, overload_lengths):
     return int(m * frac * 1.25) + 4096
 
 
+class _Handle(namedtuple("_Handle", "n flags masks k ws tile_rows")):
+    """A counted and scanned multi-set selection (DeviceSelect.msel_masks):
+    rows, their flags, the k masks (ctypes ints), the workspace as mgr_scan
+    left it.  Opaque to the exchange."""
+    __slots__ = ()
+
+    @property
+    def args(self):
+        """The selection as every mgr_msel_* pack / unpack call takes it."""
+        return (self.n, _lib.ptr(self.flags), self.k, self.masks, self.tile_rows,
+                _lib.ptr(self.ws))
+
+
+def _field_args(srcs, row_bytes):
+    """(fields, their source pointers, their row bytes) of a multi-field pack."""
+    nf = len(srcs)
+    return (nf, (ctypes.c_void_p * nf)(*[_lib.ptr(t) for t in srcs]),
+            (ctypes.c_int64 * nf)(*row_bytes))
+
+
 class DeviceSelect:
     """Selections on the GPU: face flags (mgr_halo_flags) and multi-set
     selections (mgr_msel_count + mgr_scan + mgr_msel_pack)."""
@@ -329,10 +453,9 @@ class DeviceSelect:
         """The inverse of msel_pack with an add (mgr_msel_unpack_add): for
         every set k with srcs[k] not None, in ascending order, the rows of
         ``acc_flat`` in the set += srcs[k]'s rows, in row order."""
-        n, flags, cb, k, ws, tile_rows = handle
-        ptrs = (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in srcs])
-        _lib.call("mgr_msel_unpack_add", _lib.ptr(acc_flat), int(elem), int(ncomp), n,
-                  _lib.ptr(flags), k, cb, tile_rows, _lib.ptr(ws), ptrs, _lib.stream_handle())
+        ptrs = (ctypes.c_void_p * handle.k)(*[None if t is None else t.data_ptr() for t in srcs])
+        _lib.call("mgr_msel_unpack_add", _lib.ptr(acc_flat), int(elem), int(ncomp), *handle.args,
+                  ptrs, _lib.stream_handle())
 
     def flags(self, pos_flat, n, ncols, code, dim, hi, lo):
         f = torch.empty(max(n, 1), dtype=torch.int16, device=self.dev)
@@ -360,42 +483,33 @@ class DeviceSelect:
         _lib.call("mgr_msel_count", _lib.ptr(flags), n, k, cb, tile_rows, _lib.ptr(ws), s)
         _lib.alg_add("halo", 2 * n)                        # the flags, read once
         _lib.call("mgr_scan", n, k, tile_rows, _lib.ptr(ws), _lib.ptr(counts), s)
-        return (n, flags, cb, k, ws, tile_rows), counts
+        return _Handle(n, flags, cb, k, ws, tile_rows), counts
 
     def msel_pack(self, handle, src_flat, row_bytes, dsts):
         """One field's selected rows: set k's rows, in row order, to dsts[k]
         (a flat uint8 tensor, or None: set k not written)."""
-        n, flags, cb, k, ws, tile_rows = handle
-        ptrs = (ctypes.c_void_p * k)(*[None if t is None else _lib.ptr(t) for t in dsts])
-        _lib.call("mgr_msel_pack", _lib.ptr(src_flat), row_bytes, n, _lib.ptr(flags), k, cb,
-                  tile_rows, _lib.ptr(ws), ptrs, _lib.stream_handle())
+        ptrs = (ctypes.c_void_p * handle.k)(*[None if t is None else _lib.ptr(t) for t in dsts])
+        _lib.call("mgr_msel_pack", _lib.ptr(src_flat), row_bytes, *handle.args, ptrs,
+                  _lib.stream_handle())
 
     def msel_pack_fields(self, handle, srcs, row_bytes, dsts, rows_out=0):
         """Several fields (at most _lib.MSEL_MAX_FIELDS) of the same rows in
         one pass: dsts[f][k] as in msel_pack (field 0's None entries decide
         which sets are written).
         ``rows_out``: the rows the written sets hold (byte accounting)."""
-        n, flags, cb, k, ws, tile_rows = handle
-        _lib.alg_add("halo_pack", 2 * n + 2 * rows_out * sum(row_bytes))
-        nf = len(srcs)
-        sp = (ctypes.c_void_p * nf)(*[_lib.ptr(t) for t in srcs])
-        rb = (ctypes.c_int64 * nf)(*row_bytes)
-        dp = (ctypes.c_void_p * (nf * k))(*[None if t is None else _lib.ptr(t)
-                                             for row in dsts for t in row])
-        _lib.call("mgr_msel_pack_fields", nf, sp, rb, n, _lib.ptr(flags), k, cb, tile_rows,
-                  _lib.ptr(ws), dp, _lib.stream_handle())
+        _lib.alg_add("halo_pack", 2 * handle.n + 2 * rows_out * sum(row_bytes))
+        dp = (ctypes.c_void_p * (len(srcs) * handle.k))(*[None if t is None else _lib.ptr(t)
+                                                          for row in dsts for t in row])
+        _lib.call("mgr_msel_pack_fields", *_field_args(srcs, row_bytes), *handle.args, dp,
+                  _lib.stream_handle())
 
     def msel_pack_placed(self, handle, srcs, row_bytes, dsts, cap_rows):
         """msel_pack_fields with the sets back to back from dsts[f] at the
         scan's set starts, rows beyond cap_rows not written: launched before
         the set sizes are known on the host."""
-        n, flags, cb, k, ws, tile_rows = handle
-        nf = len(srcs)
-        sp = (ctypes.c_void_p * nf)(*[_lib.ptr(t) for t in srcs])
-        rb = (ctypes.c_int64 * nf)(*row_bytes)
-        dp = (ctypes.c_void_p * nf)(*[_lib.ptr(t) for t in dsts])
-        _lib.call("mgr_msel_pack_placed", nf, sp, rb, n, _lib.ptr(flags), k, cb, tile_rows,
-                  _lib.ptr(ws), dp, int(cap_rows), _lib.stream_handle())
+        dp = (ctypes.c_void_p * len(srcs))(*[_lib.ptr(t) for t in dsts])
+        _lib.call("mgr_msel_pack_placed", *_field_args(srcs, row_bytes), *handle.args, dp,
+                  int(cap_rows), _lib.stream_handle())
 
     def to_host(self, tensors):
         """One device->host read of several small int64 tensors (one sync)."""
@@ -408,6 +522,94 @@ class DeviceSelect:
     @staticmethod
     def to_host_wait(read):
         return host_read_wait(read)
+
+
+class _Store:
+    """The append-only overload store: per field (payload, positions when
+    carried, flags) a flat tensor and the row where the overload rows start,
+    the capacity in rows and the rows so far (``m``).  Built on ``arena`` (the
+    flags field's store is always the exchange's own) or on nothing: the
+    first ``ensure`` then allocates."""
+
+    def __init__(self, rbs, dev, arena=None, multi=False, carry_pos=False):
+        self.rbs, self.dev, self.m = rbs, dev, 0
+        self.st, self.base, self.cap, self.in_arena = None, None, 0, False
+        if arena is not None:
+            self.cap, self.in_arena = arena[3], True
+            self.st = _arena_stores(arena, multi, carry_pos) + [
+                torch.empty(max(self.cap, 1) * 2, dtype=torch.uint8, device=dev)]
+            self.base = [arena[2]] * (len(rbs) - 1) + [0]
+
+    def rows(self, f, row0=0, rows=None):
+        """Field f's store from overload row ``row0`` on (``rows`` rows of it)."""
+        o = (self.base[f] + row0) * self.rbs[f]
+        return self.st[f][o:] if rows is None else self.st[f][o:o + rows * self.rbs[f]]
+
+    def ensure(self, new_m):
+        """Room for new_m rows: outgrown, the rows so far move once to a store
+        of the exchange's own with headroom."""
+        if self.st is not None and new_m <= self.cap:
+            return
+        ncap = max(2 * new_m, 1024)
+        nst = [torch.empty(ncap * rb, dtype=torch.uint8, device=self.dev) for rb in self.rbs]
+        for f, rb in enumerate(self.rbs):
+            if self.m:
+                nst[f][: self.m * rb].copy_(self.rows(f, 0, self.m))
+        self.st, self.base, self.cap, self.in_arena = nst, [0] * len(nst), ncap, False
+
+
+class _LocalSends:
+    """Where the local rows' sends are packed.  ``pieces[d]``: the rows this
+    rank sends in dimension d to a (step 1) and to b (step 2), 0 for a side
+    that does not send.  The sets of every dimension whose neighbours are
+    other ranks are staged back to back in one buffer per field
+    (``halo_local<f>``), so one pass packs them all; the sets of a self
+    dimension go straight into the store, where the receives would land --
+    dimension 0's in that first pass (its place is known), a later one's when
+    that dimension comes (its place depends on the earlier receives)."""
+
+    def __init__(self, sel, lh, srcs, rbs, nb, selfd, sent):
+        self.sel, self.lh, self.srcs, self.rbs, self.selfd = sel, lh, srcs, rbs, selfd
+        self.pieces = [(int(sent[2 * d]) if keep_a else 0, int(sent[2 * d + 1]) if keep_b else 0)
+                       for d, (_, _, keep_a, keep_b) in enumerate(nb)]
+        self.off, off = {}, 0
+        for d, p in enumerate(self.pieces):
+            if not selfd[d]:
+                self.off[d] = off
+                off += sum(p)
+        self.buf = [sel._buf(f"halo_local{f}", off * rb) for f, rb in enumerate(rbs)]
+
+    def staged(self, d, f, side):
+        """Field f's staged rows of dimension d to a (side 0) or b (side 1)."""
+        o = self.off[d] + (self.pieces[d][0] if side else 0)
+        return self.buf[f][o * self.rbs[f]:(o + self.pieces[d][side]) * self.rbs[f]]
+
+    def pack(self, dims, store=None, ia=0, ib=0):
+        """One pass packing the sets of ``dims``; a self dimension among them
+        lands in ``store``: step 1 (to a = me) at ib, step 2 (to b = me) at ia."""
+        dsts = [[None] * (2 * len(self.pieces)) for _ in self.rbs]
+        for d in dims:
+            for f in range(len(self.rbs)):
+                for side, at in enumerate((ib, ia)):
+                    if self.pieces[d][side]:
+                        dsts[f][2 * d + side] = store.rows(f, at, self.pieces[d][side]) \
+                            if self.selfd[d] else self.staged(d, f, side)
+        if any(t is not None for t in dsts[0]):
+            self.sel.msel_pack_fields(self.lh, self.srcs, self.rbs, dsts,
+                                      sum(sum(self.pieces[d]) for d in dims))
+
+
+def _unwrap_step(R, d, box, store, f, pos_code, ncols, s):
+    """The rows dimension d appended (field f: the positions), shifted to the
+    image beside this cell: [ia, ib) came from a (+L on the last cell),
+    [ib, ib + from_b) from b (-L on the first)."""
+    rows = s.from_a + s.from_b
+    up = box[d] if int(R.rank_cell_index[d]) == int(R.grid_topology[d]) - 1 else 0.0
+    down = -box[d] if int(R.rank_cell_index[d]) == 0 else 0.0
+    if rows and (up or down):
+        e = [0.0] * R.dim
+        shift_regions(store.rows(f, s.ia, rows), pos_code, ncols, R.dim, [s.from_a, rows],
+                      [e[:d] + [up] + e[d + 1:], e[:d] + [down] + e[d + 1:]])
 
 
 def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n,
@@ -480,16 +682,6 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     rbs = rbds + ([ncols * isz] if carry_pos else []) + [2]
     F, FL = len(rbs), len(rbs) - 1                        # fields; the flags field
 
-    steps = []                                            # per dimension, for the route
-
-    def result(out, rows, in_arena):
-        """out: the fields' overload rows (payload, then positions)."""
-        res = (out[:D] if multi else out[0]), (out[D] if carry_pos else None), rows, in_arena
-        if not return_route:
-            return res
-        for name in ["msel_ws_local"] + [f"msel_ws_ghost{d}" for d in range(dim)]:
-            sel.take(name)   # the route owns the workspaces from here on
-        return res + (HaloRoute(R, n, rows, flags, lh=lh, nb=nb, selfd=selfd, steps=steps),)
     me = transport.rank
     nb = [neighbours(R, d, periodic) for d in range(dim)]
     selfd = [a == me and b == me for a, b, _, _ in nb]
@@ -500,202 +692,60 @@ def exchange_overload(R, transport, data_flat, rbd, pos_flat, ncols, pos_code, n
     for c in pending:   # (the general path reads them here)
         check_counts(c.cpu().numpy(), [])
 
-    # 1. the local rows' counts of every dimension's two selections, one pass
-    S = 2 * dim
-    lh, lcount = sel.msel(flags, n, list(range(S)), "_local")
-    # 2. local counts to the neighbours (step 1 then step 2 of every dimension)
-    send_l = torch.zeros(S, dtype=torch.int64, device=dev)
-    send_l.copy_(_encode_counts(lcount))
-    for d, (a, b, keep_a, keep_b) in enumerate(nb):
-        if not keep_a:
-            send_l[2 * d].zero_()
-        if not keep_b:
-            send_l[2 * d + 1].zero_()
-    recv_l = torch.zeros(S, dtype=torch.int64, device=dev)   # [from_b, from_a] per dimension
-    ops = []
-    for d, (a, b, _, _) in enumerate(nb):
-        ops += [("send", a, send_l[2 * d:2 * d + 1].view(torch.uint8)),
-                ("recv", b, recv_l[2 * d:2 * d + 1].view(torch.uint8)),
-                ("send", b, send_l[2 * d + 1:2 * d + 2].view(torch.uint8)),
-                ("recv", a, recv_l[2 * d + 1:2 * d + 2].view(torch.uint8))]
-    _p2p(transport, ops)
-    ls, rl = sel.to_host([send_l, recv_l])                   # host sync 1
-    # a failed selection scan (here, or at a neighbour through its messages)
-    # travels as the failure bit; sizes stay consistent, the ranks agree at
-    # the end of the exchange
-    ls, f1 = _decode(ls)
-    rl, f2 = _decode(rl)
-    failed = f1 or f2
-
-    # the append-only overload store: data (+ positions) + flags
-    st = [None] * F
-    base, cap, in_arena = 0, 0, False
-    if arena is not None:
-        st[:D] = list(arena[0]) if multi else [arena[0]]
-        if carry_pos:
-            st[D] = arena[1]
-        base, cap, in_arena = arena[2], arena[3], True
-        st[FL] = torch.empty(max(cap, 1) * 2, dtype=torch.uint8, device=dev)
-    fbase = [base] * (F - 1) + [0]                           # the flags store is our own
-    m = 0
-
-    def store(f, row0=0, rows=None):
-        o = (fbase[f] + row0) * rbs[f]
-        return st[f][o:] if rows is None else st[f][o:o + rows * rbs[f]]
-
-    def ensure(new_m):
-        nonlocal st, fbase, cap, in_arena
-        if st[0] is not None and new_m <= cap:
-            return
-        # outgrew the store: a store of its own with headroom, rows so far moved once
-        ncap = max(2 * new_m, 1024)
-        nst = [torch.empty(ncap * rb, dtype=torch.uint8, device=dev) for rb in rbs]
-        for f in range(F):
-            if m:
-                nst[f][: m * rbs[f]].copy_(store(f, 0, m))
-        st, fbase, cap, in_arena = nst, [0] * F, ncap, False
-
-    def local_pieces(d):
-        """Rows this rank sends in dimension d: its local piece then its
-        buffer piece, to a (step 1) and to b (step 2)."""
-        a, b, keep_a, keep_b = nb[d]
-        return (int(ls[2 * d]) if keep_a else 0), (int(ls[2 * d + 1]) if keep_b else 0)
-
-    # local sends staged for the neighbours: every non-self dimension's sets
-    # (and dimension 0's, whose place in the store is known now) in one pass;
-    # the sets of a later self dimension are written straight into the store
-    # when that dimension comes (their place depends on the earlier receives)
-    stage_off, off = {}, 0
-    for d in range(dim):
-        if not selfd[d]:
-            nla, nlb = local_pieces(d)
-            stage_off[d] = off
-            off += nla + nlb
-    lbuf = [sel._buf(f"halo_local{f}", off * rbs[f]) for f in range(F)]
-
-    def local_dsts(d, f, ia, ib):
-        """Set -> destination of dimension d's local pieces, field f."""
-        nla, nlb = local_pieces(d)
-        rb = rbs[f]
-        if selfd[d]:   # step 1 (to a = me) lands at ib, step 2 (to b = me) at ia
-            return {2 * d: store(f, ib, nla) if nla else None,
-                    2 * d + 1: store(f, ia, nlb) if nlb else None}
-        o = stage_off[d]
-        return {2 * d: lbuf[f][o * rb:(o + nla) * rb] if nla else None,
-                2 * d + 1: lbuf[f][(o + nla) * rb:(o + nla + nlb) * rb] if nlb else None}
-
-    def pack_local(dims, places):
-        dsts = [[None] * S for _ in range(F)]
-        for d in dims:
-            for f in range(F):
-                for k, t in local_dsts(d, f, *places.get(d, (0, 0))).items():
-                    dsts[f][k] = t
-        if any(t is not None for t in dsts[0]):
-            sel.msel_pack_fields(lh, srcs, rbs, dsts, sum(sum(local_pieces(d)) for d in dims))
-
-    def unwrap_dim(d, ia, ib, new_m):
-        """The rows dimension d appended, shifted to the image beside this
-        cell: [ia, ib) came from a (+L on the last cell), [ib, new_m) from b
-        (-L on the first)."""
-        if not (unwrap and periodic) or new_m == ia:
-            return
-        up = box[d] if int(R.rank_cell_index[d]) == int(R.grid_topology[d]) - 1 else 0.0
-        down = -box[d] if int(R.rank_cell_index[d]) == 0 else 0.0
-        if up or down:
-            e = [0.0] * dim
-            shift_regions(store(D, ia, new_m - ia), pos_code, ncols, dim, [ib - ia, new_m - ia],
-                          [e[:d] + [up] + e[d + 1:], e[:d] + [down] + e[d + 1:]])
-
-    first = [d for d in range(dim) if not selfd[d] or d == 0]
+    # 1. the local rows' counts of every dimension's two selections, one pass,
+    # swapped with the neighbours of every dimension                (host sync 1)
+    lh, lcount = sel.msel(flags, n, list(range(2 * dim)), "_local")
+    sent, rl, failed = _swap_counts(transport, sel, dev, lcount, nb, False)
+    # 2. the store, and the first pack of the local sends
+    store = _Store(rbs, dev, arena, multi, carry_pos)
+    local = _LocalSends(sel, lh, srcs, rbs, nb, selfd, sent)
     if selfd[0]:
-        nla, nlb = local_pieces(0)
-        ensure(nla + nlb)
-    pack_local(first, {0: (0, local_pieces(0)[1])} if selfd[0] else {})
+        store.ensure(sum(local.pieces[0]))
+    local.pack([d for d in range(dim) if not selfd[d] or d == 0], store, 0, local.pieces[0][1])
 
-    for d, (a, b, keep_a, keep_b) in enumerate(nb):
-        sa, sb = 2 * d, 2 * d + 1
-        # 3. the buffer's selections for this dimension (rows received so far)
-        gc = np.zeros(2, dtype=np.int64)
-        rg = np.zeros(2, dtype=np.int64)
-        gh = None
+    steps = []                                            # per dimension, for the route
+    for d, (a, b, _, _) in enumerate(nb):
+        # 3. the buffer's selections for this dimension (rows received so far),
+        # their counts swapped from d = 1 on              (host sync per dimension)
+        m, gh, gcount = store.m, None, None
+        gc = rg = (0, 0)
         if d > 0:
-            send_g = torch.zeros(2, dtype=torch.int64, device=dev)
-            recv_g = torch.zeros(2, dtype=torch.int64, device=dev)
             if m:
-                gh, gcount = sel.msel(store(FL, 0, m).view(torch.int16), m, [sa, sb],
+                gh, gcount = sel.msel(store.rows(FL, 0, m).view(torch.int16), m, [2 * d, 2 * d + 1],
                                       f"_ghost{d}" if return_route else "_ghost")
-                send_g.copy_(_encode_counts(gcount))
-            if failed:   # keep announcing it: the neighbours' neighbours learn too
-                send_g.fill_(_FAIL)
-            if not keep_a:
-                send_g[0].zero_()
-            if not keep_b:
-                send_g[1].zero_()
-            _p2p(transport, [("send", a, send_g[0:1].view(torch.uint8)),
-                           ("recv", b, recv_g[0:1].view(torch.uint8)),
-                           ("send", b, send_g[1:2].view(torch.uint8)),
-                           ("recv", a, recv_g[1:2].view(torch.uint8))])
-            gc, rg = sel.to_host([send_g, recv_g])            # host sync per dimension
-            gc, f1 = _decode(gc)
-            rg, f2 = _decode(rg)
-            # (sizes stay as announced -- the neighbours post receives of them)
-            failed = failed or f1 or f2
-        nla, nlb = local_pieces(d)
-        nga, ngb = int(gc[0]), int(gc[1])
+            gc, rg, failed = _swap_counts(transport, sel, dev, gcount, [nb[d]], failed)
         # what it receives: from_b (step 1) and from_a (step 2), each a local
-        # piece and a buffer piece of the sender
-        rlb, rla = int(rl[sa]), int(rl[sb])
-        rgb, rga = int(rg[0]), int(rg[1])
-        new_m = m + rla + rga + rlb + rgb
-        ensure(new_m)
-        # concat(buffer, from_a, from_b) (redist.py:305): appended in place
-        ia, ib = m, m + rla + rga
+        # piece and a buffer piece of the sender, appended in place
+        rlb, rla, rgb, rga = int(rl[2 * d]), int(rl[2 * d + 1]), int(rg[0]), int(rg[1])
+        s = Step(*local.pieces[d], int(gc[0]), int(gc[1]), rla, rga, rlb, rgb,
+                 ia=m, ib=m + rla + rga, m=m, gh=gh)
+        store.ensure(s.end)
         if return_route:
-            steps.append(dict(nla=nla, nlb=nlb, nga=nga, ngb=ngb, rla=rla, rga=rga, rlb=rlb,
-                              rgb=rgb, ia=ia, ib=ib, m=m, gh=gh))
+            steps.append(s)
         if selfd[d] and d > 0:
-            pack_local([d], {d: (ia, ib)})
-        gsz = nga + ngb
-        gbuf = None
-        if gsz:
+            local.pack([d], store, s.ia, s.ib)
+        gbuf, ng = None, s.nga + s.ngb
+        if ng:   # the buffer's pieces: staged, or on a self dimension after the local ones
             if selfd[d]:
-                gd = [[store(f, ib + nla, nga) if nga else None,
-                       store(f, ia + nlb, ngb) if ngb else None] for f in range(F)]
+                gd = [[store.rows(f, s.ib + s.nla, s.nga) if s.nga else None,
+                       store.rows(f, s.ia + s.nlb, s.ngb) if s.ngb else None] for f in range(F)]
             else:
-                gbuf = [sel._buf(f"halo_ghost{f}", gsz * rbs[f]) for f in range(F)]
-                gd = [[gbuf[f][: nga * rbs[f]] if nga else None,
-                       gbuf[f][nga * rbs[f]:gsz * rbs[f]] if ngb else None] for f in range(F)]
-            sel.msel_pack_fields(gh, [store(f, 0, m) for f in range(F)], rbs, gd, gsz)
-        if selfd[d]:
-            unwrap_dim(d, ia, ib, new_m)
-            m = new_m
-            continue
-        ops = []
-        o = stage_off[d]
-        for step in (1, 2):
-            to, frm = (a, b) if step == 1 else (b, a)
-            nl, ng = (nla, nga) if step == 1 else (nlb, ngb)
-            lo_, go_ = (o, 0) if step == 1 else (o + nla, nga)
-            rl_, rg_, at = (rlb, rgb, ib) if step == 1 else (rla, rga, ia)
-            for f in range(F):
-                rb = rbs[f]
-                if nl:
-                    ops.append(("send", to, lbuf[f][lo_ * rb:(lo_ + nl) * rb]))
-                if ng:
-                    ops.append(("send", to, gbuf[f][go_ * rb:(go_ + ng) * rb]))
-                if rl_:
-                    ops.append(("recv", frm, store(f, at, rl_)))
-                if rg_:
-                    ops.append(("recv", frm, store(f, at + rl_, rg_)))
-        _p2p(transport, ops)
-        unwrap_dim(d, ia, ib, new_m)
-        m = new_m
+                gbuf = [sel._buf(f"halo_ghost{f}", ng * rbs[f]) for f in range(F)]
+                gd = [[gbuf[f][: s.nga * rbs[f]] if s.nga else None,
+                       gbuf[f][s.nga * rbs[f]:ng * rbs[f]] if s.ngb else None] for f in range(F)]
+            sel.msel_pack_fields(gh, [store.rows(f, 0, m) for f in range(F)], rbs, gd, ng)
+        if not selfd[d]:
+            _p2p(transport, _forward_group(s, d, a, b, store, local, gbuf))
+        if unwrap and periodic:
+            _unwrap_step(R, d, box, store, D, pos_code, ncols, s)
+        store.m = s.end
     # one agreement per call: every rank raises together if any scan failed
     if transport.any_failed(failed):
         check_counts([-1], [])
-    if not m:
-        return result([torch.empty(0, dtype=torch.uint8, device=dev)] * (F - 1), 0, in_arena)
-    return result([store(f, 0, m) for f in range(F - 1)], m, in_arena)
+    route = (["msel_ws_local"] + [f"msel_ws_ghost{d}" for d in range(dim)],
+             dict(owner=R, n_local=n, flags=flags, lh=lh, nb=nb, selfd=selfd, steps=steps))
+    return _result(sel, dev, (D, multi, carry_pos), [store.rows(f, 0, store.m) for f in range(FL)],
+                   store.m, store.in_arena, route if return_route else None)
 
 
 ELEM_BYTES = {_lib.MGR_ELEM_F32: 4, _lib.MGR_ELEM_F64: 8, _lib.MGR_ELEM_I32: 4,
@@ -749,9 +799,9 @@ def reduce_overload(R, transport, route, local_acc, halo_vals, elem, ncomp, sel=
             sel.msel_unpack_add(route._self, accs[f], elems[f], ncomps[f], srcs)
         return
     steps, dim = route._steps, len(route._steps)
-    if not route.n_halo and not any(s["nla"] + s["nlb"] for s in steps):
+    if not route.n_halo and not any(s.nla + s.nlb for s in steps):
         return
-    nst = max([s["nla"] + s["nga"] + s["nlb"] + s["ngb"] for s in steps] + [1])
+    nst = max([s.to_a + s.to_b for s in steps] + [1])
     S, stage = [], []
     for f in range(nf):
         S.append(sel._buf(f"halo_red_store{f}", route.n_halo * ebs[f]))
@@ -759,38 +809,20 @@ def reduce_overload(R, transport, route, local_acc, halo_vals, elem, ncomp, sel=
         stage.append(sel._buf(f"halo_red_stage{f}", nst * ebs[f]))
     for d in range(dim - 1, -1, -1):
         s = steps[d]
-        a, b = route._nb[d][0], route._nb[d][1]
-        nla, nlb, nga, ngb = s["nla"], s["nlb"], s["nga"], s["ngb"]
-        ia, ib, na, nb_ = s["ia"], s["ib"], s["nla"] + s["nga"], s["nlb"] + s["ngb"]
-        back_a, back_b = s["rla"] + s["rga"], s["rlb"] + s["rgb"]
         if not route._selfd[d]:
-            # the forward messages with sender and receiver swapped; towards a
-            # pair of ranks the sends and the receives match in posting order
-            # (a == b on a grid extent of 2)
-            ops = []
-            for f in range(nf):
-                eb = ebs[f]
-                if back_b:
-                    ops.append(("send", b, S[f][ib * eb:(ib + back_b) * eb]))
-                if na:
-                    ops.append(("recv", a, stage[f][: na * eb]))
-                if back_a:
-                    ops.append(("send", a, S[f][ia * eb:(ia + back_a) * eb]))
-                if nb_:
-                    ops.append(("recv", b, stage[f][na * eb:(na + nb_) * eb]))
-            _p2p(transport, ops)
+            _p2p(transport, _backward_group(s, route._nb[d][0], route._nb[d][1], S, stage, ebs))
         for f in range(nf):
             eb = ebs[f]
             if route._selfd[d]:   # step 1 (to a = me) landed at ib, step 2 at ia
-                la, ga = S[f][ib * eb:], S[f][(ib + nla) * eb:]
-                lb, gb = S[f][ia * eb:], S[f][(ia + nlb) * eb:]
+                la, ga = S[f][s.ib * eb:], S[f][(s.ib + s.nla) * eb:]
+                lb, gb = S[f][s.ia * eb:], S[f][(s.ia + s.nlb) * eb:]
             else:
-                la, ga = stage[f], stage[f][nla * eb:]
-                lb, gb = stage[f][na * eb:], stage[f][(na + nlb) * eb:]
-            if nla or nlb:
+                la, ga = stage[f], stage[f][s.nla * eb:]
+                lb, gb = stage[f][s.to_a * eb:], stage[f][(s.to_a + s.nlb) * eb:]
+            if s.nla or s.nlb:
                 srcs = [None] * (2 * dim)
-                srcs[2 * d], srcs[2 * d + 1] = (la if nla else None), (lb if nlb else None)
+                srcs[2 * d], srcs[2 * d + 1] = (la if s.nla else None), (lb if s.nlb else None)
                 sel.msel_unpack_add(route._lh, accs[f], elems[f], ncomps[f], srcs)
-            if nga or ngb:
-                sel.msel_unpack_add(s["gh"], S[f][: s["m"] * eb], elems[f], ncomps[f],
-                                    [ga if nga else None, gb if ngb else None])
+            if s.nga or s.ngb:
+                sel.msel_unpack_add(s.gh, S[f][: s.m * eb], elems[f], ncomps[f],
+                                    [ga if s.nga else None, gb if s.ngb else None])
