@@ -457,43 +457,42 @@ int mgr_msel_pack(const void* src, int64_t row_bytes, int64_t n, const uint16_t*
                                 dsts, stream);
 }
 
-int mgr_msel_pack_fields(int nfields, const void* const* srcs, const int64_t* row_bytes, int64_t n,
-                         const uint16_t* flags, int nsets, const int* masks, int tile_rows,
-                         const void* workspace, void* const* dsts, void* stream) {
+// mgr_msel_pack_fields (placed false: dsts[f * nsets + k] per set, cap_rows
+// unused) and mgr_msel_pack_placed (every set of field f from dsts[f], at most
+// cap_rows rows) share every check.
+static int msel_pack(int nfields, const void* const* srcs, const int64_t* row_bytes, int64_t n,
+                     const uint16_t* flags, int nsets, const int* masks, int tile_rows,
+                     const void* workspace, void* const* dsts, bool placed, int64_t cap_rows,
+                     void* stream) {
     int rc = check_tile(tile_rows);
     if (rc || (rc = check_sets(nsets, masks))) return rc;
     if (nfields < 1 || nfields > MGR_MSEL_MAX_FIELDS || !srcs || !row_bytes)
         return fail(MGR_EINVAL, "nfields %d (1..%d)", nfields, MGR_MSEL_MAX_FIELDS);
+    if (placed && cap_rows < 0) return fail(MGR_EINVAL, "cap_rows %lld", (long long)cap_rows);
     for (int f = 0; f < nfields; ++f)
         if (row_bytes[f] < 1) return fail(MGR_EINVAL, "row_bytes %lld", (long long)row_bytes[f]);
     if (n > 0 && (!flags || !workspace || !dsts)) return fail(MGR_EINVAL, "null argument");
     for (int f = 0; n > 0 && f < nfields; ++f)
-        if (!srcs[f]) return fail(MGR_EINVAL, "null argument");
-    if (n <= 0) return MGR_OK;
+        if (!srcs[f] || (placed && cap_rows > 0 && !dsts[f])) return fail(MGR_EINVAL, "null argument");
+    if (n <= 0 || (placed && cap_rows == 0)) return MGR_OK;
     const mgr::Workspace ws = mgr::carve((void*)workspace, n, nsets, tile_rows);
     HIP_OK(mgr::launch_msel_pack(nfields, srcs, row_bytes, n, flags, nsets, masks, tile_rows, ws,
-                                 dsts, (hipStream_t)stream));
+                                 dsts, (hipStream_t)stream, placed ? cap_rows : -1));
     return MGR_OK;
+}
+
+int mgr_msel_pack_fields(int nfields, const void* const* srcs, const int64_t* row_bytes, int64_t n,
+                         const uint16_t* flags, int nsets, const int* masks, int tile_rows,
+                         const void* workspace, void* const* dsts, void* stream) {
+    return msel_pack(nfields, srcs, row_bytes, n, flags, nsets, masks, tile_rows, workspace, dsts,
+                     false, -1, stream);
 }
 
 int mgr_msel_pack_placed(int nfields, const void* const* srcs, const int64_t* row_bytes, int64_t n,
                          const uint16_t* flags, int nsets, const int* masks, int tile_rows,
                          const void* workspace, void* const* dsts, int64_t cap_rows, void* stream) {
-    int rc = check_tile(tile_rows);
-    if (rc || (rc = check_sets(nsets, masks))) return rc;
-    if (nfields < 1 || nfields > MGR_MSEL_MAX_FIELDS || !srcs || !row_bytes)
-        return fail(MGR_EINVAL, "nfields %d (1..%d)", nfields, MGR_MSEL_MAX_FIELDS);
-    if (cap_rows < 0) return fail(MGR_EINVAL, "cap_rows %lld", (long long)cap_rows);
-    for (int f = 0; f < nfields; ++f)
-        if (row_bytes[f] < 1) return fail(MGR_EINVAL, "row_bytes %lld", (long long)row_bytes[f]);
-    if (n > 0 && (!flags || !workspace || !dsts)) return fail(MGR_EINVAL, "null argument");
-    for (int f = 0; n > 0 && f < nfields; ++f)
-        if (!srcs[f] || (cap_rows > 0 && !dsts[f])) return fail(MGR_EINVAL, "null argument");
-    if (n <= 0 || cap_rows == 0) return MGR_OK;
-    const mgr::Workspace ws = mgr::carve((void*)workspace, n, nsets, tile_rows);
-    HIP_OK(mgr::launch_msel_pack(nfields, srcs, row_bytes, n, flags, nsets, masks, tile_rows, ws,
-                                 dsts, (hipStream_t)stream, cap_rows));
-    return MGR_OK;
+    return msel_pack(nfields, srcs, row_bytes, n, flags, nsets, masks, tile_rows, workspace, dsts,
+                     true, cap_rows, stream);
 }
 
 int mgr_msel_unpack_add(void* acc, int elem, int ncomp, int64_t n, const uint16_t* flags,
@@ -614,39 +613,71 @@ int mgr_bin_starts(int64_t n, int nbins, int tile_rows, const void* workspace,
     return MGR_OK;
 }
 
-int mgr_pack(const void* src, int64_t row_bytes, int64_t n, const void* dest, int nbins,
-             int drop_bin, int tile_rows, const void* workspace, void* dst, int redirect_bin,
-             void* redirect_dst, void* stream) {
+// The tiles [tile_begin, tile_end) of ws.T as the range the launch covers
+// (ws.t0, ws.tn).  all_ok: tile_end < 0 stands for every tile (tile_begin
+// unused), which mgr_pack_tiles refuses.  *empty: the range holds no tile,
+// nothing is to be launched.
+static int apply_tiles(mgr::Workspace& ws, int64_t tile_begin, int64_t tile_end, bool all_ok,
+                       bool* empty) {
+    *empty = false;
+    if (all_ok && tile_end < 0) return MGR_OK;
+    if (tile_begin < 0 || tile_end < tile_begin || tile_end > ws.T)
+        return fail(MGR_EINVAL, "tiles [%lld, %lld) of %lld", (long long)tile_begin,
+                    (long long)tile_end, (long long)ws.T);
+    *empty = tile_end == tile_begin;
+    ws.t0 = tile_begin;
+    ws.tn = tile_end - tile_begin;
+    return MGR_OK;
+}
+
+static int check_nbins(int nbins) {
+    if (nbins < 1 || nbins > MGR_MAX_BINS) return fail(MGR_EINVAL, "nbins %d", nbins);
+    return MGR_OK;
+}
+
+// mgr_pack, mgr_pack_ids (ids_src is required) and mgr_pack_tiles (the tile
+// range must be given; the other two cover every tile and ignore it).  n < 0
+// and a null dst are not refused.
+enum class PackEntry { kPack, kPackIds, kPackTiles };
+static int pack_one(PackEntry entry, const void* src, int64_t row_bytes, int64_t n, const void* dest, int nbins,
+                    int drop_bin, int tile_rows, const void* workspace, void* dst, int redirect_bin,
+                    void* redirect_dst, const uint16_t* ids_src, uint16_t* ids_dst,
+                    uint16_t* ids_redirect_dst, int64_t tile_begin, int64_t tile_end,
+                    void* stream) {
     int rc = check_tile(tile_rows);
     if (rc) return rc;
     if (row_bytes < 1) return fail(MGR_EINVAL, "row_bytes %lld", (long long)row_bytes);
-    if (nbins < 1 || nbins > MGR_MAX_BINS) return fail(MGR_EINVAL, "nbins %d", nbins);
-    if (n > 0 && (!src || !dest || !workspace)) return fail(MGR_EINVAL, "null argument");
-    if (n > 0 && redirect_bin >= 0 && !redirect_dst) return fail(MGR_EINVAL, "redirect without buffer");
+    if ((rc = check_nbins(nbins))) return rc;
+    if (n > 0 && (!src || !dest || !workspace || (entry == PackEntry::kPackIds && !ids_src)))
+        return fail(MGR_EINVAL, "null argument");
+    if (n > 0 && redirect_bin >= 0 && (!redirect_dst || (ids_src && !ids_redirect_dst)))
+        return fail(MGR_EINVAL, "redirect without buffer");
     if (redirect_bin >= nbins) return fail(MGR_EINVAL, "redirect_bin out of range");
-    const mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
+    mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
+    bool empty = false;
+    if (entry == PackEntry::kPackTiles && (rc = apply_tiles(ws, tile_begin, tile_end, false, &empty))) return rc;
+    if (empty) return MGR_OK;
     HIP_OK(mgr::launch_pack(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst,
-                            redirect_bin, redirect_dst, (hipStream_t)stream));
+                            redirect_bin, redirect_dst, (hipStream_t)stream, ids_src, ids_dst,
+                            ids_redirect_dst));
     return MGR_OK;
+}
+
+int mgr_pack(const void* src, int64_t row_bytes, int64_t n, const void* dest, int nbins,
+             int drop_bin, int tile_rows, const void* workspace, void* dst, int redirect_bin,
+             void* redirect_dst, void* stream) {
+    return pack_one(PackEntry::kPack, src, row_bytes, n, dest, nbins, drop_bin, tile_rows,
+                    workspace, dst, redirect_bin, redirect_dst, nullptr, nullptr, nullptr, 0, 0,
+                    stream);
 }
 
 int mgr_pack_ids(const void* src, int64_t row_bytes, int64_t n, const void* dest, int nbins,
                  int drop_bin, int tile_rows, const void* workspace, void* dst, int redirect_bin,
                  void* redirect_dst, const uint16_t* ids_src, uint16_t* ids_dst,
                  uint16_t* ids_redirect_dst, void* stream) {
-    int rc = check_tile(tile_rows);
-    if (rc) return rc;
-    if (row_bytes < 1) return fail(MGR_EINVAL, "row_bytes %lld", (long long)row_bytes);
-    if (nbins < 1 || nbins > MGR_MAX_BINS) return fail(MGR_EINVAL, "nbins %d", nbins);
-    if (n > 0 && (!src || !dest || !workspace || !ids_src)) return fail(MGR_EINVAL, "null argument");
-    if (n > 0 && redirect_bin >= 0 && (!redirect_dst || !ids_redirect_dst))
-        return fail(MGR_EINVAL, "redirect without buffer");
-    if (redirect_bin >= nbins) return fail(MGR_EINVAL, "redirect_bin out of range");
-    const mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
-    HIP_OK(mgr::launch_pack(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst,
-                            redirect_bin, redirect_dst, (hipStream_t)stream, ids_src, ids_dst,
-                            ids_redirect_dst));
-    return MGR_OK;
+    return pack_one(PackEntry::kPackIds, src, row_bytes, n, dest, nbins, drop_bin, tile_rows,
+                    workspace, dst, redirect_bin, redirect_dst, ids_src, ids_dst, ids_redirect_dst,
+                    0, 0, stream);
 }
 
 int mgr_pack_tiles(const void* src, int64_t row_bytes, int64_t n, const void* dest, int nbins,
@@ -654,25 +685,9 @@ int mgr_pack_tiles(const void* src, int64_t row_bytes, int64_t n, const void* de
                    void* redirect_dst, const uint16_t* ids_src, uint16_t* ids_dst,
                    uint16_t* ids_redirect_dst, int64_t tile_begin, int64_t tile_end,
                    void* stream) {
-    int rc = check_tile(tile_rows);
-    if (rc) return rc;
-    if (row_bytes < 1) return fail(MGR_EINVAL, "row_bytes %lld", (long long)row_bytes);
-    if (nbins < 1 || nbins > MGR_MAX_BINS) return fail(MGR_EINVAL, "nbins %d", nbins);
-    if (n > 0 && (!src || !dest || !workspace)) return fail(MGR_EINVAL, "null argument");
-    if (n > 0 && redirect_bin >= 0 && (!redirect_dst || (ids_src && !ids_redirect_dst)))
-        return fail(MGR_EINVAL, "redirect without buffer");
-    if (redirect_bin >= nbins) return fail(MGR_EINVAL, "redirect_bin out of range");
-    mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
-    if (tile_begin < 0 || tile_end < tile_begin || tile_end > ws.T)
-        return fail(MGR_EINVAL, "tiles [%lld, %lld) of %lld", (long long)tile_begin,
-                    (long long)tile_end, (long long)ws.T);
-    if (tile_end == tile_begin) return MGR_OK;
-    ws.t0 = tile_begin;
-    ws.tn = tile_end - tile_begin;
-    HIP_OK(mgr::launch_pack(src, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, dst,
-                            redirect_bin, redirect_dst, (hipStream_t)stream, ids_src, ids_dst,
-                            ids_redirect_dst));
-    return MGR_OK;
+    return pack_one(PackEntry::kPackTiles, src, row_bytes, n, dest, nbins, drop_bin, tile_rows,
+                    workspace, dst, redirect_bin, redirect_dst, ids_src, ids_dst, ids_redirect_dst,
+                    tile_begin, tile_end, stream);
 }
 
 int64_t mgr_onepass_workspace_bytes(int64_t n, int nbins) {
@@ -762,7 +777,7 @@ int mgr_pack_fields(int nfields, const void* const* srcs, const int64_t* row_byt
     if (rc) return rc;
     if (nfields < 1 || nfields > MGR_MAX_FIELDS) return fail(MGR_EINVAL, "nfields %d", nfields);
     if (!srcs || !row_bytes || !dsts) return fail(MGR_EINVAL, "null field arrays");
-    if (nbins < 1 || nbins > MGR_MAX_BINS) return fail(MGR_EINVAL, "nbins %d", nbins);
+    if ((rc = check_nbins(nbins))) return rc;
     if (redirect_bin >= nbins) return fail(MGR_EINVAL, "redirect_bin out of range");
     for (int f = 0; f < nfields; ++f) {
         if (row_bytes[f] < 1) return fail(MGR_EINVAL, "field %d: row_bytes %lld", f, (long long)row_bytes[f]);
@@ -775,14 +790,9 @@ int mgr_pack_fields(int nfields, const void* const* srcs, const int64_t* row_byt
         return fail(MGR_EINVAL, "redirect without an ids buffer");
     if (n > 0 && ids_src && !ids_dst) return fail(MGR_EINVAL, "ids without an output");
     mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
-    if (tile_end >= 0) {
-        if (tile_begin < 0 || tile_end < tile_begin || tile_end > ws.T)
-            return fail(MGR_EINVAL, "tiles [%lld, %lld) of %lld", (long long)tile_begin,
-                        (long long)tile_end, (long long)ws.T);
-        if (tile_end == tile_begin) return MGR_OK;
-        ws.t0 = tile_begin;
-        ws.tn = tile_end - tile_begin;
-    }
+    bool empty = false;
+    if ((rc = apply_tiles(ws, tile_begin, tile_end, true, &empty))) return rc;
+    if (empty) return MGR_OK;
     HIP_OK(mgr::launch_pack_fields(nfields, srcs, row_bytes, n, dest, nbins, drop_bin, tile_rows,
                                    ws, dsts, redirect_bin, redirect_bin >= 0 ? redirect_dsts : nullptr,
                                    (hipStream_t)stream, ids_src, ids_dst, ids_redirect_dst));
@@ -798,7 +808,7 @@ int mgr_unpack_fields(int nfields, const void* const* packed, const int64_t* row
     if (rc) return rc;
     if (nfields < 1 || nfields > MGR_MAX_FIELDS) return fail(MGR_EINVAL, "nfields %d", nfields);
     if (!packed || !row_bytes || !outs) return fail(MGR_EINVAL, "null field arrays");
-    if (nbins < 1 || nbins > MGR_MAX_BINS) return fail(MGR_EINVAL, "nbins %d", nbins);
+    if ((rc = check_nbins(nbins))) return rc;
     if (n < 0) return fail(MGR_EINVAL, "n < 0");
     if (redirect_bin >= nbins) return fail(MGR_EINVAL, "redirect_bin out of range");
     if (redirect_bin >= 0 && redirect_bin == drop_bin)
@@ -817,14 +827,9 @@ int mgr_unpack_fields(int nfields, const void* const* packed, const int64_t* row
         return MGR_OK;
     }
     mgr::Workspace ws = mgr::carve((void*)workspace, n, nbins, tile_rows);
-    if (tile_end >= 0) {
-        if (tile_begin < 0 || tile_end < tile_begin || tile_end > ws.T)
-            return fail(MGR_EINVAL, "tiles [%lld, %lld) of %lld", (long long)tile_begin,
-                        (long long)tile_end, (long long)ws.T);
-        if (tile_end == tile_begin) return MGR_OK;
-        ws.t0 = tile_begin;
-        ws.tn = tile_end - tile_begin;
-    }
+    bool empty = false;
+    if ((rc = apply_tiles(ws, tile_begin, tile_end, true, &empty))) return rc;
+    if (empty) return MGR_OK;
     HIP_OK(mgr::launch_unpack_fields(nfields, packed, row_bytes, n, dest, nbins, drop_bin,
                                      tile_rows, ws, outs, redirect_bin, redirect_srcs,
                                      (hipStream_t)stream));

@@ -1,5 +1,5 @@
 // Device-side building blocks shared by the kernel translation units
-// (mgr_bin.hip, mgr_pack.hip, mgr_kernels.hip): IEEE/x86-exact scalar math
+// (mgr_bin.hip, the pack and unpack files, mgr_kernels.hip): IEEE/x86-exact scalar math
 // of the reference's wrap and binning, wave primitives, the packs' round
 // ranking and tagged slots, one-pass scan words, streaming load/store
 // policies, XCD-aware tile order; plus launch helpers.
@@ -1037,6 +1037,18 @@ __device__ __forceinline__ int64_t xcd_tile_c(int64_t bid, int64_t T, int C) {
 // xcd > 0: in XCD chunks of xcd tiles (kXcdPackChunk); 0: in launch order.
 __device__ __forceinline__ int64_t tile_index(int64_t t0, int64_t tn, int xcd) {
     return t0 + (xcd ? xcd_tile_c(blockIdx.x, tn, xcd) : (int64_t)blockIdx.x);
+}
+
+// The same from a launch's tile context (TileCtx, mgr_internal.h).
+__device__ __forceinline__ int64_t tile_index(const TileCtx& c) {
+    return tile_index(c.t0, c.tn, c.xcd);
+}
+__device__ __forceinline__ bool scan_failed(const TileCtx& c) { return scan_failed(c.scan_err); }
+__device__ __forceinline__ long long seg_start(const TileCtx& c, int64_t tile, int b) {
+    return seg_start(c.offsets, c.bin_starts, c.T, tile, b, c.redirect_bin);
+}
+__device__ __forceinline__ SegLoad seg_load(const TileCtx& c, int64_t tile, int lane) {
+    return seg_load(c.offsets, c.bin_starts, c.T, tile, lane, c.nb, c.redirect_bin);
 }
 
 // Streaming accesses: NT selects the nontemporal (nt) cache policy for data

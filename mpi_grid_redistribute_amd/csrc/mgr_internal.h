@@ -115,6 +115,49 @@ Workspace carve(void* base, int64_t n, int nbins, int tile_rows);
 int dest_bytes(int nbins);
 int nbits_for(int nbins);
 
+// Shipped constants that were A/B knobs (DESIGN.md §3.3 records the A/Bs).
+constexpr int kXcdPackChunk = 16;   // packs: tiles dealt to the XCDs in chunks of 16
+constexpr int kImgRoundsPerWave = 2;  // image pack: 64-row rounds per wave
+
+// What a tile-walking pack or unpack kernel needs to know about its tiles,
+// passed by value (kernarg segment) in place of a positional scalar list;
+// device-side accessors (seg_start, tile_index, scan_failed): mgr_device.h.
+struct TileCtx {
+    const void* dest;            // [n] every row's bin, dest_bytes(nb) bytes each
+    const int64_t* offsets;      // Workspace::offsets, [nb][T]
+    const int64_t* bin_starts;   // Workspace::bin_starts, [nb + 1]
+    const uint32_t* scan_err;    // Workspace::scan_err
+    int64_t n;
+    int64_t T, t0, tn;           // the launch covers tiles [t0, t0 + tn) of T
+    int tile_rows;
+    int nb, nbits;               // bins, ceil(log2(nb)) for the ballot match
+    int drop_bin, redirect_bin;  // < 0: none
+    int xcd;                     // tiles dealt to the XCDs in chunks of xcd (tile_index)
+    // a selection pack (2 bins, one dropped: the halo's rows to send): the
+    // kernels that know it skip the loads of dropped rows
+    __host__ __device__ bool selection() const { return nb <= 2 && drop_bin >= 0; }
+};
+static inline TileCtx tile_ctx(int64_t n, const void* dest, int nbins, int drop_bin, int tile_rows,
+                               const Workspace& ws, int redirect_bin) {
+    return TileCtx{dest, ws.offsets, ws.bin_starts, ws.scan_err, n, ws.T, ws.t0, ws.tn, tile_rows,
+                   nbins, nbits_for(nbins), drop_bin, redirect_bin, kXcdPackChunk};
+}
+
+// The 2-byte side field of a pack (mgr_pack_ids: the fine cells or halo
+// flags travelling with the rows), passed to the kernels by value (src NULL:
+// none).  SideField: the same on the host, handed down the launchers; the
+// coop and image launchers take it into their kernel and mark it used, other
+// paths leave it to a second (2-byte-row) pack.
+struct SideIds {
+    const uint16_t* src;
+    uint16_t* dst;
+    uint16_t* red;
+};
+struct SideField {
+    SideIds ids;
+    bool used;
+};
+
 // Kernel ids for the profiler.
 enum KernelId { K_BIN_COUNT, K_SCAN, K_PACK, K_CELL_IDS, K_BIN_IDS, K_CELLNUM_IDX, K_SYNTH,
                 K_EXCHANGE, K_HALO, K_BIN_FINE, K_COUNT_IDS, K_PACK_FINE, K_PACK_NARROW,
@@ -257,9 +300,27 @@ struct ScanTest {
 const Hooks& hooks();
 int set_hook(const char* key, int64_t value);   // mgr_test_hook
 
-// Shipped constants that were A/B knobs (DESIGN.md §3.3 records the A/Bs).
-constexpr int kXcdPackChunk = 16;   // packs: tiles dealt to the XCDs in chunks of 16
-constexpr int kImgRoundsPerWave = 2;  // image pack: 64-row rounds per wave
+// One pack or unpack as the launchers hand it down: the array, the stream,
+// the side field (packs; may be NULL), the launch's snapshot of the test
+// hooks and the tile context.  A pack reads src and writes dst, the redirect
+// bin's rows to `redirect`; an unpack reads src (the packed rows) and, for
+// the redirect bin's rows, `redirect` (never written), and writes dst (the
+// output in source order).  A multi-field launch fills no array (all null):
+// its arrays travel in the kernels' own tables.
+struct PackJob {
+    const void* src;
+    int64_t row_bytes;
+    void* dst;
+    void* redirect;   // the redirect bin's buffer; NULL without a redirect bin
+    hipStream_t s;
+    SideField* side;
+    const Hooks& h;
+    TileCtx c;
+};
+// The single-array pack kernels for one array of a context (mgr_pack.hip):
+// launch_pack's body, and launch_pack_fields' per-field fallback.
+hipError_t launch_pack_array(const void* src, int64_t row_bytes, const TileCtx& c, void* dst,
+                             void* redirect_dst, hipStream_t s, const SideIds& ids);
 
 // log2 of the widest copy unit (<= 16 bytes) that divides every address and
 // size or-ed into a.

@@ -16,7 +16,8 @@
 // original row order, which is what makes the ballot ranks stable.
 
 //
-// Translation units: mgr_bin.hip (binning), mgr_pack.hip (pack), this file
+// Translation units: mgr_bin.hip (binning), mgr_pack.hip, mgr_pack_fields.hip
+// and mgr_msel_pack.hip (packs), mgr_unpack.hip (unpacks), this file
 // (test hooks, workspace, scan, halo selection, synthetic input); shared
 // device helpers in mgr_device.h.
 

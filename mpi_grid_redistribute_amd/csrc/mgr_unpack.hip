@@ -1,7 +1,7 @@
 // Unpack kernels (gfx950): the return path, the inverse of the packs of
-// mgr_pack.hip.  For the (dest, nbins, drop_bin, tile_rows, workspace,
-// redirect_bin) of a pack, slot(r) is the row at which that pack writes
-// source row r (redist.py:195-199, send_buff[i] = data[rank_to_send == i],
+// mgr_pack.hip and mgr_pack_fields.hip.  For the (dest, nbins, drop_bin,
+// tile_rows, workspace, redirect_bin) of a pack, slot(r) is the row at which
+// that pack writes source row r (redist.py:195-199, send_buff[i] = data[rank_to_send == i],
 // order kept -- the permutation being inverted); the unpack writes
 // out[r] = packed[slot(r)] (redirect_src[slot(r)] for a row of redirect_bin,
 // zero bytes for a row of drop_bin).  The slot arithmetic is the pack's own
@@ -21,27 +21,25 @@ constexpr int kUnpackCoopRounds = 16;   // cooperative unpack tiles: <= 1024 row
 // kWide (rows > 256 B): the wave copies one row at a time, 64 lanes wide.
 template <int W, typename DestT, bool kWide>
 __global__ __launch_bounds__(kBlock) void unpack_kernel(
-    const uint8_t* __restrict__ packed, int64_t upr /* W-units per row */, int64_t n,
-    const DestT* __restrict__ dest, int nb, int nbits, int drop_bin,
-    const int64_t* __restrict__ offsets, const int64_t* __restrict__ bin_starts, int64_t T,
-    int64_t t0, int64_t tn, int tile_rows, int per_wave_lds, uint8_t* __restrict__ out,
-    int redirect_bin, const uint8_t* __restrict__ redirect_src,
-    const uint32_t* __restrict__ scan_err) {
+    TileCtx c, const uint8_t* __restrict__ packed, int64_t upr /* W-units per row */,
+    int per_wave_lds, uint8_t* __restrict__ out, const uint8_t* __restrict__ redirect_src) {
     using U = typename Unit<W>::T;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int w = threadIdx.x >> 6, lane = lane_id();
     const int64_t tl = (int64_t)blockIdx.x * (blockDim.x >> 6) + w;
-    if (tl >= tn || scan_failed(scan_err)) return;
-    const int64_t tile = t0 + tl;
+    if (tl >= c.tn || scan_failed(c)) return;
+    const int64_t tile = c.t0 + tl;
+    const int nb = c.nb, drop_bin = c.drop_bin, redirect_bin = c.redirect_bin;
+    const DestT* __restrict__ dest = (const DestT*)c.dest;
     int64_t* goff = (int64_t*)(smem + w * per_wave_lds);
     int32_t* run = (int32_t*)(smem + w * per_wave_lds + align16(nb * 8));
     for (int b = lane; b < nb; b += 64) {
-        goff[b] = seg_start(offsets, bin_starts, T, tile, b, redirect_bin);
+        goff[b] = seg_start(c, tile, b);
         run[b] = 0;
     }
     wave_sync();
-    const int64_t row0 = tile * (int64_t)tile_rows;
-    const int rows = (int)min((int64_t)tile_rows, n - row0);
+    const int64_t row0 = tile * (int64_t)c.tile_rows;
+    const int rows = (int)min((int64_t)c.tile_rows, c.n - row0);
     const U* __restrict__ p_u = (const U*)packed;
     const U* __restrict__ r_u = (const U*)redirect_src;
     U* __restrict__ o_u = (U*)out;
@@ -50,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void unpack_kernel(
         const bool valid = r0 + lane < rows;
         const int64_t row = row0 + r0 + lane;
         const unsigned b = valid ? (unsigned)dest[row] : 0u;
-        const unsigned long long peers = match_bin(b, valid, nbits);
+        const unsigned long long peers = match_bin(b, valid, c.nbits);
         const int rk = rank_in(peers);
         int64_t slot = 0;
         if (valid) slot = goff[b] + run[b] + rk;
@@ -147,28 +145,26 @@ struct UnpackFieldPtrs {
 
 template <int U0, int U1, int U2, int U3>
 __global__ __launch_bounds__(1024) void unpack_coop_kernel(
-    UnpackFieldPtrs fp, int64_t n, const uint8_t* __restrict__ dest, int nb, int nbits,
-    int drop_bin, const int64_t* __restrict__ offsets, const int64_t* __restrict__ bin_starts,
-    int64_t T, int64_t t0, int64_t tn, int tile_rows, int redirect_bin, int xcd,
-    const uint32_t* __restrict__ scan_err) {
+    TileCtx c, UnpackFieldPtrs fp) {
     __shared__ int s_cnt[kUnpackCoopRounds][64];
     const int w = threadIdx.x >> 6, lane = lane_id();
-    const int64_t tile = tile_index(t0, tn, xcd);
-    const int64_t row0 = tile * (int64_t)tile_rows + 64 * w;
-    const int nr = (int)max((int64_t)0, min((int64_t)64, n - row0));
+    const int64_t tile = tile_index(c);
+    const int64_t row0 = tile * (int64_t)c.tile_rows + 64 * w;
+    const int nr = (int)max((int64_t)0, min((int64_t)64, c.n - row0));
+    const uint8_t* __restrict__ dest = (const uint8_t*)c.dest;
     const unsigned b = lane < nr ? (unsigned)dest[row0 + lane] : 0u;
     long long tbase = 0;
-    if (lane < nb) tbase = seg_start(offsets, bin_starts, T, tile, lane, redirect_bin);
+    if (lane < c.nb) tbase = seg_start(c, tile, lane);
     // rank inside the round; lane l counts bin l
     const bool valid = lane < nr;
     unsigned long long pe;
-    s_cnt[w][lane] = round_rank(b, valid, lane, nbits, &pe);
+    s_cnt[w][lane] = round_rank(b, valid, lane, c.nbits, &pe);
     __syncthreads();
-    if (scan_failed(scan_err)) return;
+    if (scan_failed(c)) return;
     for (int j = 0; j < w; ++j) tbase += s_cnt[j][lane];
     const long long base = __shfl(tbase, (int)b, 64);
     long long tgt = -1;
-    if (valid && (int)b != drop_bin) tgt = tag_slot(base + rank_in(pe), (int)b, redirect_bin);
+    if (valid && (int)b != c.drop_bin) tgt = tag_slot(base + rank_in(pe), (int)b, c.redirect_bin);
     CoopGather<U0> f0;
     CoopGather<U1> f1;
     CoopGather<U2> f2;
@@ -189,39 +185,29 @@ static bool coop_shape(int nbins, int tile_rows) {
     return nbins <= 64 && dest_bytes(nbins) == 1 && tile_rows <= 64 * kUnpackCoopRounds;
 }
 
-// The tile context of an unpack, as the cooperative launchers share it.
-struct UnpackTiles {
-    int64_t n;
-    const void* dest;
-    int nbins, drop_bin, tile_rows;
-    const Workspace& ws;
-    int redirect_bin;
-    hipStream_t s;
-};
+static_assert(std::is_trivially_copyable<UnpackFieldPtrs>::value &&
+              sizeof(TileCtx) + sizeof(UnpackFieldPtrs) <= 4096,
+              "unpack_coop_kernel's arguments: copied bytewise, at most 4 KB");
 
+// The unpacks take a PackJob (mgr_internal.h) read backwards: src = the
+// packed rows, redirect = the redirect bin's source (read only), dst = the output.
 template <int A, int B, int C, int D>
-static hipError_t launch_unpack_coop(const UnpackFieldPtrs& fp, const UnpackTiles& t) {
-    const Workspace& ws = t.ws;
-    hipLaunchKernelGGL((unpack_coop_kernel<A, B, C, D>), dim3((unsigned)ws.tn),
-                       dim3(t.tile_rows), 0, t.s, fp, t.n, (const uint8_t*)t.dest, t.nbins,
-                       nbits_for(t.nbins), t.drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0,
-                       ws.tn, t.tile_rows, t.redirect_bin, kXcdPackChunk, ws.scan_err);
+static hipError_t launch_unpack_coop(const UnpackFieldPtrs& fp, const PackJob& j) {
+    hipLaunchKernelGGL((unpack_coop_kernel<A, B, C, D>), dim3((unsigned)j.c.tn),
+                       dim3(j.c.tile_rows), 0, j.s, j.c, fp);
     return hipGetLastError();
 }
 
 // One field through the cooperative kernel (hipErrorNotSupported: not its shape).
-static hipError_t unpack_coop(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
-                              int nbins, int drop_bin, int tile_rows, const Workspace& ws,
-                              void* out, int redirect_bin, const void* red, hipStream_t s) {
-    if (!coop_shape(nbins, tile_rows)) return hipErrorNotSupported;
-    const int u = coop_unit(packed, row_bytes, out, red);
+static hipError_t unpack_coop(const PackJob& j) {
+    if (!coop_shape(j.c.nb, j.c.tile_rows)) return hipErrorNotSupported;
+    const int u = coop_unit(j.src, j.row_bytes, j.dst, j.redirect);
     if (u < 0) return hipErrorNotSupported;
     UnpackFieldPtrs fp{};
-    fp.packed[0] = (const uint8_t*)packed;
-    fp.red[0] = (const uint8_t*)red;
-    fp.out[0] = (uint8_t*)out;
-    const UnpackTiles t{n, dest, nbins, drop_bin, tile_rows, ws, redirect_bin, s};
-#define MGR_UC1(W_, N_) case W_ * 32 + N_: return launch_unpack_coop<W_ * 32 + N_, 0, 0, 0>(fp, t);
+    fp.packed[0] = (const uint8_t*)j.src;
+    fp.red[0] = (const uint8_t*)j.redirect;
+    fp.out[0] = (uint8_t*)j.dst;
+#define MGR_UC1(W_, N_) case W_ * 32 + N_: return launch_unpack_coop<W_ * 32 + N_, 0, 0, 0>(fp, j);
     switch (u) {
         MGR_UC1(16, 1) MGR_UC1(16, 2) MGR_UC1(16, 3) MGR_UC1(16, 4)
         MGR_UC1(8, 1) MGR_UC1(8, 2) MGR_UC1(8, 3) MGR_UC1(8, 4)
@@ -237,12 +223,11 @@ static hipError_t unpack_coop(const void* packed, int64_t row_bytes, int64_t n, 
 }
 
 // 2..4 fields of a signature pack_coop_fields takes, from one ranking
-// (hipErrorNotSupported otherwise).
+// (hipErrorNotSupported otherwise).  t: the tile context and stream (no array).
 static hipError_t unpack_coop_fields(int nf, const void* const* packed, const int64_t* row_bytes,
-                                     int64_t n, const void* dest, int nbins, int drop_bin,
-                                     int tile_rows, const Workspace& ws, void* const* outs,
-                                     int redirect_bin, const void* const* reds, hipStream_t s) {
-    if (!coop_shape(nbins, tile_rows)) return hipErrorNotSupported;
+                                     void* const* outs, const void* const* reds,
+                                     const PackJob& t) {
+    if (!coop_shape(t.c.nb, t.c.tile_rows)) return hipErrorNotSupported;
     int u[4] = {0, 0, 0, 0};
     UnpackFieldPtrs fp{};
     for (int f = 0; f < nf; ++f) {
@@ -255,8 +240,7 @@ static hipError_t unpack_coop_fields(int nf, const void* const* packed, const in
     auto sig = [&](int a, int b, int c, int d) { return u[0] == a && u[1] == b && u[2] == c && u[3] == d; };
     constexpr int F4x1 = 4 * 32 + 1, F4x3 = 4 * 32 + 3, F8x1 = 8 * 32 + 1, F8x3 = 8 * 32 + 3,
                   F16x2 = 16 * 32 + 2, F4x9 = 4 * 32 + 9, F16x1 = 16 * 32 + 1, F8x2 = 8 * 32 + 2;
-    const UnpackTiles t{n, dest, nbins, drop_bin, tile_rows, ws, redirect_bin, s};
-    // the field sets of pack_coop_fields (mgr_pack.hip)
+    // the field sets of pack_coop_fields (mgr_pack_fields.hip)
     if (sig(F4x3, F4x3, F4x1, F8x1)) return launch_unpack_coop<F4x3, F4x3, F4x1, F8x1>(fp, t);
     if (sig(F8x3, F8x1, 0, 0)) return launch_unpack_coop<F8x3, F8x1, 0, 0>(fp, t);
     if (sig(F16x2, F8x3, 0, 0)) return launch_unpack_coop<F16x2, F8x3, 0, 0>(fp, t);
@@ -270,56 +254,42 @@ static hipError_t unpack_coop_fields(int nf, const void* const* packed, const in
 }
 
 template <int W, typename DestT, bool kWide>
-static hipError_t unpack_t(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
-                           int nb, int drop_bin, int tile_rows, const Workspace& ws, void* out,
-                           int redirect_bin, const void* red, hipStream_t s) {
+static hipError_t unpack_t(const PackJob& j) {
     auto k = unpack_kernel<W, DestT, kWide>;
-    const int per_wave = align16(nb * 8) + align16(nb * 4);
+    const int per_wave = align16(j.c.nb * 8) + align16(j.c.nb * 4);
     const int wpb = waves_per_block(per_wave);
     const int lds = per_wave * wpb;
     ensure_lds(k, lds);
-    const int64_t grid = (ws.tn + wpb - 1) / wpb;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * wpb), (size_t)lds, s,
-                       (const uint8_t*)packed, row_bytes / W, n, (const DestT*)dest, nb,
-                       nbits_for(nb), drop_bin, ws.offsets, ws.bin_starts, ws.T, ws.t0, ws.tn,
-                       tile_rows, per_wave, (uint8_t*)out, redirect_bin, (const uint8_t*)red,
-                       ws.scan_err);
+    const int64_t grid = (j.c.tn + wpb - 1) / wpb;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * wpb), (size_t)lds, j.s, j.c,
+                       (const uint8_t*)j.src, j.row_bytes / W, per_wave, (uint8_t*)j.dst,
+                       (const uint8_t*)j.redirect);
     return hipGetLastError();
 }
 
 template <int W>
-static hipError_t unpack_w(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
-                           int nb, int drop_bin, int tile_rows, const Workspace& ws, void* out,
-                           int redirect_bin, const void* red, hipStream_t s) {
-    const bool wide = row_bytes > 256;
-    if (dest_bytes(nb) == 1)
-        return wide ? unpack_t<W, uint8_t, true>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s)
-                    : unpack_t<W, uint8_t, false>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
-    return wide ? unpack_t<W, uint16_t, true>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s)
-                : unpack_t<W, uint16_t, false>(packed, row_bytes, n, dest, nb, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+static hipError_t unpack_w(const PackJob& j) {
+    const bool wide = j.row_bytes > 256;
+    if (dest_bytes(j.c.nb) == 1)
+        return wide ? unpack_t<W, uint8_t, true>(j) : unpack_t<W, uint8_t, false>(j);
+    return wide ? unpack_t<W, uint16_t, true>(j) : unpack_t<W, uint16_t, false>(j);
 }
 
-// One field: the cooperative kernel where it takes the shape (hook
-// unpack_kernel 1: never), else the generic one in the widest unit dividing
-// the row and every base address.
-static hipError_t unpack_rows(const void* packed, int64_t row_bytes, int64_t n, const void* dest,
-                              int nbins, int drop_bin, int tile_rows, const Workspace& ws,
-                              void* out, int redirect_bin, const void* red, hipStream_t s,
-                              const Hooks& h) {
-    if (redirect_bin < 0) red = nullptr;
-    if (h.unpack_kernel != 1) {
-        const hipError_t e = unpack_coop(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows,
-                                         ws, out, redirect_bin, red, s);
+// One field (j.redirect null without a redirect bin): the cooperative
+// kernel where it takes the shape (hook unpack_kernel 1: never), else the
+// generic one in the widest unit dividing the row and every base address.
+static hipError_t unpack_rows(const PackJob& j) {
+    if (j.h.unpack_kernel != 1) {
+        const hipError_t e = unpack_coop(j);
         if (e != hipErrorNotSupported) return e;
     }
-    uintptr_t a = (uintptr_t)packed | (uintptr_t)out | (uintptr_t)row_bytes;
-    if (red) a |= (uintptr_t)red;
-    switch (unit_log(a)) {
-        case 4: return unpack_w<16>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
-        case 3: return unpack_w<8>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
-        case 2: return unpack_w<4>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
-        case 1: return unpack_w<2>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
-        default: return unpack_w<1>(packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws, out, redirect_bin, red, s);
+    switch (unit_log((uintptr_t)j.src | (uintptr_t)j.dst | (uintptr_t)j.row_bytes |
+                     (uintptr_t)j.redirect)) {
+        case 4: return unpack_w<16>(j);
+        case 3: return unpack_w<8>(j);
+        case 2: return unpack_w<4>(j);
+        case 1: return unpack_w<2>(j);
+        default: return unpack_w<1>(j);
     }
 }
 
@@ -333,16 +303,18 @@ hipError_t launch_unpack_fields(int nf, const void* const* packed, const int64_t
     if (n <= 0 || ws.tn <= 0) return hipSuccess;
     const Hooks& h = hooks();   // one snapshot for the whole launch
     if (redirect_bin < 0) reds = nullptr;
+    const TileCtx c = tile_ctx(n, dest, nbins, drop_bin, tile_rows, ws, redirect_bin);
     prof_begin(s, K_UNPACK);
     hipError_t e = hipErrorNotSupported;
     if (nf >= 2 && nf <= 4 && h.unpack_kernel == 0)
-        e = unpack_coop_fields(nf, packed, row_bytes, n, dest, nbins, drop_bin, tile_rows, ws,
-                               outs, redirect_bin, reds, s);
+        e = unpack_coop_fields(nf, packed, row_bytes, outs, reds,
+                               PackJob{nullptr, 0, nullptr, nullptr, s, nullptr, h, c});
     if (e == hipErrorNotSupported) {
         e = hipSuccess;
         for (int f = 0; f < nf && e == hipSuccess; ++f)
-            e = unpack_rows(packed[f], row_bytes[f], n, dest, nbins, drop_bin, tile_rows, ws,
-                            outs[f], redirect_bin, reds ? reds[f] : nullptr, s, h);
+            e = unpack_rows(PackJob{packed[f], row_bytes[f], outs[f],
+                                    reds ? (void*)reds[f] : nullptr /* read only */, s,
+                                    nullptr, h, c});
     }
     prof_end(s, K_UNPACK);
     return e;

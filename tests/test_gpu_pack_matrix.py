@@ -1,4 +1,5 @@
-"""Every pack kernel family of csrc/mgr_pack.hip against the numpy model
+"""Every pack kernel family of csrc/mgr_pack.hip (single array) and
+csrc/mgr_pack_fields.hip (multi-field) against the numpy model
 (tests/pack_model.py), straight on the C ABI, with the four options the
 product reaches only along its own diagonal: redirect bin, drop bin, tile
 ranges and the 2-byte side field.  Also mgr_tile_offsets beyond one kernarg
