@@ -541,6 +541,47 @@ int mgr_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned, 
                     int dim, const double* origin, const double* width, const int* fine,
                     const int* ghost, uint16_t* ids, uint32_t* outside, void* stream);
 
+/* ------------------------------------------- cell lists beyond 1024 cells --
+ * The large-grid mode of the ghost-cell list: 32-bit cell ids over up to
+ * MGR_MAX_WIDE_CELLS = 2^20 cells, sorted by two passes of the stable 16-bit
+ * sort (mgr_rank_ids / mgr_count_ids -> mgr_scan -> packs) over digits of at
+ * most 10 bits, least significant first; the cells' offsets come from the
+ * sorted ids.  All three calls are stream-ordered and neither allocate nor
+ * sync the host; n == 0: MGR_OK, no row is read.
+ *
+ * mgr_ghost_cells_wide: the contract of mgr_ghost_cells -- the same float64
+ * subtract, divide and floor, each rounded once; owned rows clamped into the
+ * interior block, halo rows into [0, E_d - 1] and counted in *outside; a NaN
+ * takes the lower bound; one device function computes both entries' rows --
+ * with two differences: ids are uint32, and prod(E) <= 2^20 (every E_d too).
+ * MGR_EUNSUPPORTED: pos_dtype other than MGR_F32 / MGR_F64.  MGR_EINVAL: as
+ * mgr_ghost_cells, with prod(E) > 1048576 (2^20) in place of its 1024; the
+ * product is formed without overflow.                                       */
+#define MGR_MAX_WIDE_CELLS (1 << 20)
+int mgr_ghost_cells_wide(const void* pos, int pos_dtype, int64_t n, int64_t n_owned,
+                         int64_t row_stride, int dim, const double* origin, const double* width,
+                         const int* fine, const int* ghost, uint32_t* ids, uint32_t* outside,
+                         void* stream);
+/* mgr_id_digit: out[r] = (ids[r] >> shift) & ((1 << bits) - 1) for r < n: one
+ * digit of 32-bit ids as the uint16 ids mgr_rank_ids / mgr_count_ids sort by
+ * (ids, out: device, n entries; nothing at or beyond ids + n is read).
+ * MGR_EINVAL: bits outside 1..16, shift outside 0..31, shift + bits > 32,
+ * n < 0, and for n > 0 a null ids or out.                                   */
+int mgr_id_digit(const uint32_t* ids, int64_t n, int shift, int bits, uint16_t* out, void* stream);
+/* mgr_cell_offsets: offsets[c] (device int64[ncells + 1]) = the number of
+ * rows with sorted_ids[r] < c, for c = 0..ncells -- the first row of cell c
+ * in rows sorted by their ids (device uint32[n], non-decreasing), by a lower
+ * bound per cell: work does not depend on how the rows spread over the cells.
+ * *bad (a caller-zeroed device word; NULL: not counted) gets 1 added for
+ * every row whose id is >= ncells or smaller than its predecessor's: zero
+ * proves the order and the range of the ids, in the same launch.  With a
+ * nonzero *bad the offsets are unspecified values in [0, n].  n == 0: every
+ * offset is written as 0.
+ * MGR_EINVAL: ncells outside 1..2^20, n < 0, a null offsets, and for n > 0 a
+ * null sorted_ids.                                                          */
+int mgr_cell_offsets(const uint32_t* sorted_ids, int64_t n, int64_t ncells, int64_t* offsets,
+                     uint32_t* bad, void* stream);
+
 /* ------------------------------------------------------------ exchange --
  * Replaces comm.alltoall(send_buff) + np.concatenate (redist.py:199):
  * RCCL over xGMI, one process per GPU.  The unique id is made on one rank

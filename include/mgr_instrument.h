@@ -66,7 +66,9 @@ int mgr_test_pos_modes(int pos_dtype, int box_dtype, int* wrap, int* quot);
  * "pack_fine" (the 65..1024-bin and ranked packs), "pack_narrow" (rows < 4
  * bytes), "halo_pack" (mgr_msel_pack*), "onepass" (mgr_partition_onepass),
  * "onepass_fields" (mgr_partition_onepass_fields), "unpack" (mgr_unpack,
- * mgr_unpack_fields), "unpack_ranked" (mgr_unpack_ranked_fields)) or of the
+ * mgr_unpack_fields), "unpack_ranked" (mgr_unpack_ranked_fields),
+ * "ghost_cells_wide" (mgr_ghost_cells_wide), "id_digit" (mgr_id_digit),
+ * "cell_offsets" (mgr_cell_offsets)) or of the
  * RCCL grouped row exchange
  * ("exchange").  mgr_profile_select: bit k of mask times kernel id k
  * (mgr_profile_kernel_id), default all.                                    */

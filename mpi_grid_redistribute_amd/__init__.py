@@ -12,11 +12,11 @@ exchange: native RCCL grouped send/recv.  No CPU fallback.
 from . import _lib
 from .comm import MpiHostComm, RcclComm, SelfComm, TorchDistComm, Transport
 from .halo import HaloRoute
-from .redistributor import (GridPartitioner, MPIGridRedistributor, Route, SortRoute, ghost_grid,
-                            mpi_grid_redistribute)
+from .redistributor import (CELLS_MAX, GHOST_MAX_CELLS, GridPartitioner, MPIGridRedistributor,
+                            Route, SortRoute, ghost_grid, mpi_grid_redistribute)
 
 __all__ = ["MPIGridRedistributor", "GridPartitioner", "Route", "SortRoute", "HaloRoute",
-           "mpi_grid_redistribute", "ghost_grid",
+           "mpi_grid_redistribute", "ghost_grid", "GHOST_MAX_CELLS", "CELLS_MAX",
            "RcclComm", "SelfComm", "MpiHostComm", "TorchDistComm", "Transport"]
 __version__ = "0.1.0"
 

@@ -81,6 +81,9 @@ SIGNATURES = {
     "mgr_msel_unpack_add": (_I, [_P, _I, _I, _I64, _P, _I, _P, _I, _P, _P, _P]),
     "mgr_shift_regions": (_I, [_P, _I, _I64, _I64, _I, _I, _P, _P, _P]),
     "mgr_ghost_cells": (_I, [_P, _I, _I64, _I64, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mgr_ghost_cells_wide": (_I, [_P, _I, _I64, _I64, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mgr_id_digit": (_I, [_P, _I64, _I, _I, _P, _P]),
+    "mgr_cell_offsets": (_I, [_P, _I64, _I64, _P, _P, _P]),
     "mgr_group_p2p": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "mgr_comm_unique_id": (_I, [_P]),
     "mgr_comm_create": (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
@@ -214,6 +217,9 @@ HOOK_DEFAULTS = {"tile_rounds": 0, "scan_chunk": 2048, "scan_max_chunks": 1024,
 PROFILE_KERNELS = ("bin_count", "scan", "pack", "cell_ids", "bin_ids", "cellnum_idx", "synth",
                    "exchange", "halo", "bin_fine", "count_ids", "pack_fine", "pack_narrow",
                    "halo_pack", "onepass", "onepass_fields", "unpack", "unpack_ranked")
+# The kernels of the cell lists beyond 1024 cells (sort._sort_by_wide_ids): the
+# ids that follow PROFILE_KERNELS' in the library's table.
+WIDE_PROFILE_KERNELS = ("ghost_cells_wide", "id_digit", "cell_offsets")
 
 
 _prof_on = False

@@ -100,7 +100,8 @@ const char* kernel_name(int k) {
                                                "exchange", "halo", "bin_fine", "count_ids",
                                                "pack_fine", "pack_narrow", "halo_pack",
                                                "onepass", "onepass_fields", "unpack",
-                                               "unpack_ranked"};
+                                               "unpack_ranked", "ghost_cells_wide",
+                                               "id_digit", "cell_offsets"};
     return (k >= 0 && k < K_NUM_KERNELS) ? names[k] : "?";
 }
 
@@ -936,9 +937,14 @@ int mgr_shift_regions(void* pos, int pos_dtype, int64_t n, int64_t row_stride, i
     return MGR_OK;
 }
 
-int mgr_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned, int64_t row_stride,
-                    int dim, const double* origin, const double* width, const int* fine,
-                    const int* ghost, uint16_t* ids, uint32_t* outside, void* stream) {
+// The arguments of mgr_ghost_cells and mgr_ghost_cells_wide, which differ in
+// the bound on the cells (`bound`: its name in the message) and the id type.
+// Returns MGR_OK with *launch = false for an empty call.
+static int ghost_args(int pos_dtype, int64_t n, int64_t n_owned, int64_t row_stride, int dim,
+                      const void* pos, const double* origin, const double* width, const int* fine,
+                      const int* ghost, const void* ids, int64_t max_cells, const char* bound,
+                      mgr::GhostGeom* out, bool* launch) {
+    *launch = false;
     if (pos_dtype != MGR_F32 && pos_dtype != MGR_F64)
         return fail(MGR_EUNSUPPORTED, "ghost cells: float32 / float64 positions only (dtype %d)",
                     pos_dtype);
@@ -958,8 +964,9 @@ int mgr_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned, 
         if (fine[d] < 1) return fail(MGR_EINVAL, "fine[%d] = %d < 1", d, fine[d]);
         if (ghost[d] < 0) return fail(MGR_EINVAL, "ghost[%d] = %d < 0", d, ghost[d]);
         const int64_t e = (int64_t)fine[d] + 2 * (int64_t)ghost[d];
-        if (e > 1024 || (cells *= e) > 1024)
-            return fail(MGR_EINVAL, "extended grid beyond 1024 cells (dimension %d)", d);
+        // e and the running product stay <= max_cells <= 2^20: no overflow
+        if (e > max_cells || (cells *= e) > max_cells)
+            return fail(MGR_EINVAL, "extended grid beyond %s cells (dimension %d)", bound, d);
         g.origin[d] = origin[d];
         g.width[d] = width[d];
         g.fine[d] = fine[d];
@@ -971,8 +978,58 @@ int mgr_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned, 
         g.off[d] = off;
         off *= g.ext[d];
     }
+    *out = g;
+    *launch = true;
+    return MGR_OK;
+}
+
+int mgr_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned, int64_t row_stride,
+                    int dim, const double* origin, const double* width, const int* fine,
+                    const int* ghost, uint16_t* ids, uint32_t* outside, void* stream) {
+    mgr::GhostGeom g;
+    bool launch;
+    const int rc = ghost_args(pos_dtype, n, n_owned, row_stride, dim, pos, origin, width, fine,
+                              ghost, ids, 1024, "1024", &g, &launch);
+    if (rc != MGR_OK || !launch) return rc;
     HIP_OK(mgr::launch_ghost_cells(pos, pos_dtype, n, n_owned, row_stride, dim, g, ids, outside,
                                    (hipStream_t)stream));
+    return MGR_OK;
+}
+
+// ------------------------------------------- cell lists beyond 1024 cells
+int mgr_ghost_cells_wide(const void* pos, int pos_dtype, int64_t n, int64_t n_owned,
+                         int64_t row_stride, int dim, const double* origin, const double* width,
+                         const int* fine, const int* ghost, uint32_t* ids, uint32_t* outside,
+                         void* stream) {
+    mgr::GhostGeom g;
+    bool launch;
+    const int rc = ghost_args(pos_dtype, n, n_owned, row_stride, dim, pos, origin, width, fine,
+                              ghost, ids, mgr::kMaxWideCells, "1048576 (2^20)", &g, &launch);
+    if (rc != MGR_OK || !launch) return rc;
+    HIP_OK(mgr::launch_ghost_cells_wide(pos, pos_dtype, n, n_owned, row_stride, dim, g, ids,
+                                        outside, (hipStream_t)stream));
+    return MGR_OK;
+}
+
+int mgr_id_digit(const uint32_t* ids, int64_t n, int shift, int bits, uint16_t* out, void* stream) {
+    if (bits < 1 || bits > 16) return fail(MGR_EINVAL, "bits %d not in [1, 16]", bits);
+    if (shift < 0 || shift > 31) return fail(MGR_EINVAL, "shift %d not in [0, 31]", shift);
+    if (shift + bits > 32) return fail(MGR_EINVAL, "shift %d + bits %d > 32", shift, bits);
+    if (n < 0) return fail(MGR_EINVAL, "n < 0");
+    if (n == 0) return MGR_OK;
+    if (!ids || !out) return fail(MGR_EINVAL, "null argument");
+    HIP_OK(mgr::launch_id_digit(ids, n, shift, bits, out, (hipStream_t)stream));
+    return MGR_OK;
+}
+
+int mgr_cell_offsets(const uint32_t* sorted_ids, int64_t n, int64_t ncells, int64_t* offsets,
+                     uint32_t* bad, void* stream) {
+    if (ncells < 1 || ncells > mgr::kMaxWideCells)
+        return fail(MGR_EINVAL, "ncells %lld not in [1, 1048576 (2^20)]", (long long)ncells);
+    if (n < 0) return fail(MGR_EINVAL, "n < 0");
+    if (!offsets) return fail(MGR_EINVAL, "null offsets");
+    if (n > 0 && !sorted_ids) return fail(MGR_EINVAL, "null sorted_ids");
+    HIP_OK(mgr::launch_cell_offsets(sorted_ids, n, ncells, offsets, bad, (hipStream_t)stream));
     return MGR_OK;
 }
 

@@ -8,7 +8,8 @@
 //    rank's cell (x + L or x - L), not the owner's.
 //  * ghost_cells_kernel (mgr_ghost_cells): the cell of every row in the
 //    extended grid of fine + 2 * ghost cells per dimension, as the uint16 ids
-//    mgr_rank_ids / mgr_count_ids sort by.
+//    mgr_rank_ids / mgr_count_ids sort by; as uint32 ids for grids beyond 1024
+//    cells (mgr_ghost_cells_wide, §3.12), the same kernel on the id type.
 #include "mgr_device.h"
 
 namespace mgr {
@@ -120,47 +121,62 @@ hipError_t launch_shift_regions(void* pos, int pos_dtype, int64_t n, int64_t str
 // that changed a halo row's k (NaN included) counts the row once into
 // *outside: one ballot per round, one vector atomic add by the round's first
 // lane when the round has any.  A full round's ids go out as 16 8-byte stores
-// (lane 4k gathers lanes 4k..4k+3), as the binning's side field.
+// (uint16 ids: lane 4k gathers lanes 4k..4k+3, as the binning's side field) or
+// 16 16-byte stores (uint32 ids, mgr_ghost_cells_wide: the same gather).
+
+// The one per-row arithmetic of mgr_ghost_cells and mgr_ghost_cells_wide: the
+// row's cell id; *out: a halo row whose k a clamp changed.
 template <typename T, int DIM>
+__device__ __forceinline__ unsigned ghost_cell_of(const T* __restrict__ p, bool owned, int dim_rt,
+                                                  const GhostGeom& g, bool* out) {
+    const int dim = DIM > 0 ? DIM : dim_rt;
+    unsigned id = 0;
+    bool o = false;
+#pragma unroll
+    for (int d = 0; d < dim; ++d) {
+        const double x = (double)p[d];
+        const double kd = floor((x - g.origin[d]) / g.width[d]) + (double)g.ghost[d];
+        const int lo = owned ? g.ghost[d] : 0;
+        const int hi = owned ? g.ghost[d] + g.fine[d] - 1 : g.ext[d] - 1;
+        int k;
+        if (!(kd >= (double)lo)) k = lo;           // below, or NaN
+        else if (kd > (double)hi) k = hi;
+        else k = (int)kd;
+        o = o || (!owned && !(kd >= (double)lo && kd <= (double)hi));
+        id += (unsigned)k * (unsigned)g.off[d];
+    }
+    *out = o;
+    return id;
+}
+
+template <typename T, int DIM, typename IdT>
 __global__ __launch_bounds__(kBlock) void ghost_cells_kernel(const T* __restrict__ pos, int64_t n,
                                                              int64_t n_owned, int64_t stride,
                                                              int dim_rt, GhostGeom g,
-                                                             uint16_t* __restrict__ ids,
+                                                             IdT* __restrict__ ids,
                                                              uint32_t* __restrict__ outside) {
-    const int dim = DIM > 0 ? DIM : dim_rt;
+    constexpr bool kWide = sizeof(IdT) == 4;
     const int lane = lane_id();
-    const bool ids8 = ((uintptr_t)ids & 7) == 0;
+    const bool idsv = ((uintptr_t)ids & (kWide ? 15 : 7)) == 0;   // 4 ids per vector store
     const int64_t step = (int64_t)gridDim.x * kBlock;
     for (int64_t r0 = (int64_t)blockIdx.x * kBlock + (threadIdx.x & ~63); r0 < n; r0 += step) {
         const int64_t r = r0 + lane;
         const bool valid = r < n;
         unsigned id = 0;
         bool out = false;
-        if (valid) {
-            const bool owned = r < n_owned;
-            const T* p = pos + r * stride;
-#pragma unroll
-            for (int d = 0; d < dim; ++d) {
-                const double x = (double)p[d];
-                const double kd = floor((x - g.origin[d]) / g.width[d]) + (double)g.ghost[d];
-                const int lo = owned ? g.ghost[d] : 0;
-                const int hi = owned ? g.ghost[d] + g.fine[d] - 1 : g.ext[d] - 1;
-                int k;
-                if (!(kd >= (double)lo)) k = lo;           // below, or NaN
-                else if (kd > (double)hi) k = hi;
-                else k = (int)kd;
-                out = out || (!owned && !(kd >= (double)lo && kd <= (double)hi));
-                id += (unsigned)k * (unsigned)g.off[d];
-            }
-        }
-        if (ids8 && n - r0 >= 64) {
+        if (valid) id = ghost_cell_of<T, DIM>(pos + r * stride, r < n_owned, dim_rt, g, &out);
+        if (idsv && n - r0 >= 64) {
             const unsigned v1 = __shfl_down(id, 1, 64), v2 = __shfl_down(id, 2, 64),
                            v3 = __shfl_down(id, 3, 64);
-            if ((lane & 3) == 0)
-                *(uint2*)(ids + r) = make_uint2((id & 0xffffu) | (v1 << 16),
-                                                (v2 & 0xffffu) | (v3 << 16));
+            if ((lane & 3) == 0) {
+                if constexpr (kWide)
+                    *(uint4*)(ids + r) = make_uint4(id, v1, v2, v3);
+                else
+                    *(uint2*)(ids + r) = make_uint2((id & 0xffffu) | (v1 << 16),
+                                                    (v2 & 0xffffu) | (v3 << 16));
+            }
         } else if (valid) {
-            ids[r] = (uint16_t)id;
+            ids[r] = (IdT)id;
         }
         if (outside) {
             const unsigned long long b = __ballot(out);
@@ -169,11 +185,11 @@ __global__ __launch_bounds__(kBlock) void ghost_cells_kernel(const T* __restrict
     }
 }
 
-template <typename T>
+template <typename T, typename IdT>
 static void ghost_t(const void* pos, int64_t n, int64_t n_owned, int64_t stride, int dim,
-                    const GhostGeom& g, uint16_t* ids, uint32_t* outside, hipStream_t s) {
-    auto k = dim == 1 ? ghost_cells_kernel<T, 1> : dim == 2 ? ghost_cells_kernel<T, 2>
-           : dim == 3 ? ghost_cells_kernel<T, 3> : ghost_cells_kernel<T, 0>;
+                    const GhostGeom& g, IdT* ids, uint32_t* outside, hipStream_t s) {
+    auto k = dim == 1 ? ghost_cells_kernel<T, 1, IdT> : dim == 2 ? ghost_cells_kernel<T, 2, IdT>
+           : dim == 3 ? ghost_cells_kernel<T, 3, IdT> : ghost_cells_kernel<T, 0, IdT>;
     hipLaunchKernelGGL(k, dim3(grid_for(n)), dim3(kBlock), 0, s, (const T*)pos, n, n_owned, stride,
                        dim, g, ids, outside);
 }
@@ -184,6 +200,17 @@ hipError_t launch_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t
     if (n <= 0) return hipSuccess;
     if (pos_dtype == MGR_F32) ghost_t<float>(pos, n, n_owned, stride, dim, g, ids, outside, s);
     else ghost_t<double>(pos, n, n_owned, stride, dim, g, ids, outside, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_ghost_cells_wide(const void* pos, int pos_dtype, int64_t n, int64_t n_owned,
+                                   int64_t stride, int dim, const GhostGeom& g, uint32_t* ids,
+                                   uint32_t* outside, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    prof_begin(s, K_GHOST_WIDE);
+    if (pos_dtype == MGR_F32) ghost_t<float>(pos, n, n_owned, stride, dim, g, ids, outside, s);
+    else ghost_t<double>(pos, n, n_owned, stride, dim, g, ids, outside, s);
+    prof_end(s, K_GHOST_WIDE);
     return hipGetLastError();
 }
 

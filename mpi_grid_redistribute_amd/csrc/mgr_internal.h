@@ -88,7 +88,9 @@ struct ShiftTable {
 };
 
 // mgr_ghost_cells' extended grid: ext = fine + 2 * ghost cells per dimension,
-// numbered row-major (off, last axis fastest), prod(ext) <= 1024.
+// numbered row-major (off, last axis fastest), prod(ext) <= 1024
+// (mgr_ghost_cells_wide: <= kMaxWideCells).
+constexpr int64_t kMaxWideCells = (int64_t)1 << 20;
 struct GhostGeom {
     double origin[MGR_MAX_DIM];
     double width[MGR_MAX_DIM];
@@ -161,7 +163,8 @@ struct SideField {
 // Kernel ids for the profiler.
 enum KernelId { K_BIN_COUNT, K_SCAN, K_PACK, K_CELL_IDS, K_BIN_IDS, K_CELLNUM_IDX, K_SYNTH,
                 K_EXCHANGE, K_HALO, K_BIN_FINE, K_COUNT_IDS, K_PACK_FINE, K_PACK_NARROW,
-                K_HALO_PACK, K_ONEPASS, K_ONEPASS_FIELDS, K_UNPACK, K_UNPACK_RANKED, K_NUM_KERNELS };
+                K_HALO_PACK, K_ONEPASS, K_ONEPASS_FIELDS, K_UNPACK, K_UNPACK_RANKED,
+                K_GHOST_WIDE, K_ID_DIGIT, K_CELL_OFFSETS, K_NUM_KERNELS };
 const char* kernel_name(int k);
 void prof_begin(hipStream_t s, int k);
 void prof_end(hipStream_t s, int k);
@@ -258,6 +261,16 @@ hipError_t launch_shift_regions(void* pos, int pos_dtype, int64_t n, int64_t str
 hipError_t launch_ghost_cells(const void* pos, int pos_dtype, int64_t n, int64_t n_owned,
                               int64_t stride, int dim, const GhostGeom& g, uint16_t* ids,
                               uint32_t* outside, hipStream_t s);
+// Cell lists beyond 1024 cells: the same binning with 32-bit
+// ids (mgr_ghost.hip); a digit of them as the uint16 ids the stable sort takes,
+// and the cells' offsets from the sorted ids (mgr_cells.hip).
+hipError_t launch_ghost_cells_wide(const void* pos, int pos_dtype, int64_t n, int64_t n_owned,
+                                   int64_t stride, int dim, const GhostGeom& g, uint32_t* ids,
+                                   uint32_t* outside, hipStream_t s);
+hipError_t launch_id_digit(const uint32_t* ids, int64_t n, int shift, int bits, uint16_t* out,
+                           hipStream_t s);
+hipError_t launch_cell_offsets(const uint32_t* sorted_ids, int64_t n, int64_t ncells,
+                               int64_t* offsets, uint32_t* bad, hipStream_t s);
 
 // Test hooks (include/mgr_instrument.h, mgr_test_hook): switches that make a
 // product-reachable fallback or shape run on inputs that would not take it,

@@ -47,8 +47,8 @@ from .exchange import (check_counts, exchange, exchange_back, exchange_pipelined
 from .halo import (DeviceSelect, HaloRoute, exchange_overload, halo_capacity, reduce_overload,
                    thresholds)
 from .partitioner import GridPartitioner   # noqa: F401  (re-exported, as the names below)
-from .sort import (SortRoute, _check_sort_route, _fine_sort, _IdField, _sort_by_cells,
-                   _sort_by_ids, _unsort_into, ghost_grid)
+from .sort import (CELLS_MAX, GHOST_MAX_CELLS, SortRoute, _check_sort_route,  # noqa: F401
+                   _fine_sort, _IdField, _sort_by_cells, _sort_by_ids, _unsort_into, ghost_grid)
 
 
 class Route:
@@ -694,16 +694,18 @@ class MPIGridRedistributor(_FinePlans):
         return _fine_sort(self._fine_plan(fine_cells), self._plan, self.dim, self._dev, data,
                           position, return_positions, fine_ids, return_route)
 
-    def ghost_grid(self, fine_cells, overload_lengths):
+    def ghost_grid(self, fine_cells, overload_lengths, max_cells=GHOST_MAX_CELLS):
         """(ghost, extents, origin, width) of this rank's extended fine grid
         (host numpy; the module's ``ghost_grid`` on this rank's cell): width =
         cell_length / fine_cells, ghost[d] = ceil(overload_lengths[d] /
         width[d]) layers on either side, extents = fine_cells + 2 * ghost,
-        origin = the cell's lower corner.  ValueError beyond 1024 cells."""
-        return ghost_grid(self.cell_length, self.rank_cell_limits, fine_cells, overload_lengths)
+        origin = the cell's lower corner.  ValueError beyond 1024 cells, or
+        beyond ``max_cells`` (up to CELLS_MAX = 2^20) when given."""
+        return ghost_grid(self.cell_length, self.rank_cell_limits, fine_cells, overload_lengths,
+                          max_cells)
 
     def ghost_cell_sort(self, data, position, n_local, fine_cells, overload_lengths,
-                        return_positions=False, return_route=False):
+                        return_positions=False, return_route=False, max_cells=GHOST_MAX_CELLS):
         """The cell list a neighbour search, an SPH step or a CIC/TSC deposit
         needs: this rank's owned rows AND its halo rows, stably sorted over the
         extended grid of ``ghost_grid(fine_cells, overload_lengths)`` -- the
@@ -724,25 +726,45 @@ class MPIGridRedistributor(_FinePlans):
         row beyond the ghost layers (a position that was not unwrapped, a NaN)
         is counted on the device and turns the offsets' counts to -1: host
         results raise, as after a failed scan.  One mgr_ghost_cells launch,
-        then the ranked sort of fine_cell_sort (_sort_by_ids), unchanged."""
-        ghost, ext, origin, width = self.ghost_grid(fine_cells, overload_lengths)
+        then the ranked sort of fine_cell_sort (_sort_by_ids), unchanged.
+
+        ``max_cells`` (up to CELLS_MAX = 2^20) opts into grids beyond 1024
+        cells -- the cell counts a pair loop wants, tens of rows per cell.  A
+        grid of at most 1024 cells takes the path above whatever ``max_cells``
+        is; a larger one within ``max_cells`` gets 32-bit cell ids
+        (mgr_ghost_cells_wide, the same arithmetic) and the two-digit stable
+        sort (sort._sort_by_wide_ids: two passes of the 16-bit sort over digits
+        of at most 10 bits, offsets from the sorted ids by mgr_cell_offsets).
+        Inputs, results, the SortRoute (a WideSortRoute: ``unsort`` and
+        ``return_to_source(..., sort_route=)`` take two launches) and the
+        failure convention are the same; on the device a failure turns every
+        offset to -1.  Device memory of a wide sort beside the inputs: about
+        twice the payload + 12 B/row, of its route about 8 B/row.  With
+        ``n_local = n`` and ``overload_lengths = 0`` this is a plain large
+        cell list without a halo: the supported route to more than 4096 fine
+        cells (fine_cell_sort and the one-call form keep their bounds)."""
+        ghost, ext, origin, width = self.ghost_grid(fine_cells, overload_lengths, max_cells)
         dev, outside = self._dev, []
+        wide = int(np.prod(ext)) > GHOST_MAX_CELLS
 
         def cell_ids(pos, n, fields):
             nl = int(n_local)
             if not 0 <= nl <= n:
                 raise ValueError(f"n_local {nl} outside 0..{n}")
-            ids = torch.empty(max(n, 1), dtype=torch.int16, device=dev)
+            # int32 ids: _sort_by_cells then runs the two-digit sort
+            ids = torch.empty(max(n, 1), dtype=torch.int32 if wide else torch.int16, device=dev)
             outside.append(torch.zeros(1, dtype=torch.int32, device=dev))
             fine = np.array(fine_cells).astype(np.int64)
-            _lib.call("mgr_ghost_cells", ctypes.c_void_p(pos.addr), pos.code, n, nl, pos.stride,
+            _lib.call("mgr_ghost_cells_wide" if wide else "mgr_ghost_cells",
+                      ctypes.c_void_p(pos.addr), pos.code, n, nl, pos.stride,
                       self.dim, origin.ctypes.data_as(ctypes.c_void_p),
                       width.ctypes.data_as(ctypes.c_void_p),
                       (ctypes.c_int * self.dim)(*[int(x) for x in fine]),
                       (ctypes.c_int * self.dim)(*[int(x) for x in ghost]), _lib.ptr(ids),
                       _lib.ptr(outside[0]), _lib.stream_handle())
             # read with the offsets: no sync of its own
-            return ids[:n], False, lambda counts: counts.masked_fill_(outside[0].ne(0), -1)
+            return (ids if wide else ids[:n], False,
+                    lambda counts: counts.masked_fill_(outside[0].ne(0), -1))
 
         return _sort_by_cells(
             data, position, self.dim, dev, int(np.prod(ext)), cell_ids, return_positions,

@@ -1,5 +1,6 @@
 """The stable sort by 16-bit cell ids (fine cells, ghost cells): rank or count
--> scan -> pack; the SortRoute that brings per-row results back out of sorted
+-> scan -> pack; the two-digit sort by 32-bit cell ids built on it (grids beyond
+1024 cells); the SortRoute that brings per-row results back out of sorted
 order; and the extended fine grid with ghost layers (ghost_grid)."""
 from __future__ import annotations
 
@@ -67,11 +68,47 @@ class SortRoute:
         self._ws = self._ids = self._ranks = self._tstarts = self._dest = None
 
 
+class WideSortRoute(SortRoute):
+    """The SortRoute of the two-digit sort by 32-bit cell ids
+    (``ghost_cell_sort(..., max_cells=, return_route=True)`` on a grid beyond
+    1024 cells): it owns the routes of both passes, and ``unsort`` /
+    ``return_to_source(..., sort_route=)`` undo pass 2, then pass 1, through
+    one intermediate buffer per field (two launches; the buffers, n * row
+    bytes each, live for the call only).  Memory per live route: the two
+    passes' routes -- ranked passes about 8 B/row (a digit and a rank per row
+    and pass) + 2 * T * (nb0 + nb1) + both workspaces; counted passes 2-4
+    B/row + the workspaces -- until ``release()``."""
+
+    def __init__(self, n, ncells, low, high):
+        self.n, self.nbins, self.tile_rows = int(n), int(ncells), low.tile_rows
+        self.ranked = low.ranked and high.ranked
+        self._passes = (low, high)
+
+    @property
+    def released(self):
+        return self._passes is None
+
+    def release(self):
+        """Free the route's device memory; it cannot be used afterwards."""
+        if self._passes is not None:
+            for r in self._passes:
+                r.release()
+        self._passes = None
+
+
 def _unsort_into(sroute, srcs, rbs, outs):
     """outs[f][r] = srcs[f][slot(r)] for the sort that made ``sroute``: flat
-    device tensors of sroute.n rows of rbs[f] bytes; one launch."""
+    device tensors of sroute.n rows of rbs[f] bytes; one launch (a
+    WideSortRoute: one per pass, the high digit's first)."""
     n, s = sroute.n, _lib.stream_handle()
     if n == 0:
+        return
+    if isinstance(sroute, WideSortRoute):
+        low, high = sroute._passes
+        mids = [torch.empty(max(n * rb, 1), dtype=torch.uint8, device=o.device)
+                for rb, o in zip(rbs, outs)]
+        _unsort_into(high, srcs, rbs, mids)
+        _unsort_into(low, mids, rbs, outs)
         return
     src_a, out_a = [t.data_ptr() for t in srcs], [t.data_ptr() for t in outs]
     if sroute.ranked:
@@ -151,9 +188,92 @@ def _sort_by_ids(fields, ids, n, nb, dev, scratch=None, check_ids=True, route=Fa
 
 
 GHOST_MAX_CELLS = 1024   # the ranked sort's bound (mgr_rank_ids + mgr_pack_ranked)
+CELLS_MAX = 1 << 20      # the two-digit sort's bound (mgr.h MGR_MAX_WIDE_CELLS)
+
+# How the two-digit sort cuts a cell id of ``bits`` bits: "balanced" -- a low
+# digit of ceil(bits / 2) bits: the fewest bins per pass, so the longest runs in
+# the ranked pack and the smallest tile tables -- or "low10" -- 10 low bits and
+# the rest.  Both measured once; the product uses this one.
+WIDE_SPLIT = "balanced"
 
 
-def ghost_grid(cell_length, cell_limits, fine_cells, overload_lengths):
+def _digit_split(ncells, split=None):
+    """(b0, b1, nb0, nb1): the low and high digits' bits, each <= 10, and the
+    bins of the two passes, for ids < ncells <= CELLS_MAX."""
+    if not 1 <= ncells <= CELLS_MAX:
+        raise ValueError(f"{ncells} cells: 1..{CELLS_MAX}")
+    bits = max(2, (int(ncells) - 1).bit_length())
+    split = split or WIDE_SPLIT
+    if split == "balanced":
+        b0 = (bits + 1) // 2
+    elif split == "low10":
+        b0 = min(10, bits - 1)
+    else:
+        raise ValueError(f"digit split {split!r}: 'balanced' or 'low10'")
+    b1 = bits - b0
+    return b0, b1, 1 << b0, (int(ncells) + (1 << b0) - 1) >> b0
+
+
+def _sort_by_wide_ids(fields, ids, n, ncells, dev, route=False, split=None):
+    """Stable sort of every field by 32-bit cell ids < ncells <= CELLS_MAX
+    (``ids``: an int32 device tensor of >= n entries, bits as uint32): a
+    least-significant-digit sort in two passes of _sort_by_ids over digits of
+    at most 10 bits (_digit_split).
+
+      1. low digit of the ids (mgr_id_digit); every field, and the ids as one
+         more 4-byte field, sorted by it at nb0 = 2^b0 bins;
+      2. high digit of the permuted ids (mgr_id_digit); pass 1's outputs and
+         the ids sorted by it at nb1 = ceil(ncells / 2^b0) bins;
+      3. offsets[c] = rows with id < c from the sorted ids (mgr_cell_offsets),
+         whose ``bad`` word -- an id >= ncells, or ids the two passes left out
+         of order -- turns every offset to -1 on the device, without a sync.
+
+    Each pass is _sort_by_ids unchanged: rows of 4-byte multiples <= 64 B take
+    the ranked kernels, others count + scan + the generic pack.  Pass 1's
+    outputs are dropped as soon as pass 2 is enqueued.  Peak device memory
+    beside the inputs: about twice the payload + 8 B/row (both passes' outputs
+    with their riding ids) + 4 B/row of digits + the passes' workspaces.
+    Returns ([sorted flat fields], offsets[ncells + 1] (int64, device)), and
+    with ``route`` a WideSortRoute."""
+    b0, b1, nb0, nb1 = _digit_split(ncells, split)
+    s = _lib.stream_handle()
+
+    def digit(src, shift, bits):
+        d = torch.empty(max(n, 1), dtype=torch.int16, device=dev)
+        _lib.call("mgr_id_digit", _lib.ptr(src), n, shift, bits, _lib.ptr(d), s)
+        return d[:n]
+
+    idf = _IdField(ids.view(torch.uint8).reshape(-1), 4)
+    outs1, _, *r1 = _sort_by_ids(list(fields) + [idf], digit(ids, 0, b0), n, nb0, dev,
+                                 check_ids=False, route=route)
+    mid = [_IdField(o, f.row_bytes) for o, f in zip(outs1, list(fields) + [idf])]
+    outs2, _, *r2 = _sort_by_ids(mid, digit(outs1[-1], b0, b1), n, nb1, dev, check_ids=False,
+                                 route=route)
+    del outs1, mid   # stream-ordered: pass 2 has consumed them
+    offsets = torch.empty(ncells + 1, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("mgr_cell_offsets", _lib.ptr(outs2[-1]), n, ncells, _lib.ptr(offsets),
+              _lib.ptr(bad), s)
+    offsets.masked_fill_(bad.ne(0), -1)
+    if not route:
+        return outs2[:-1], offsets
+    return outs2[:-1], offsets, WideSortRoute(n, ncells, r1[0], r2[0])
+
+
+def _wide_offsets_like(data, offsets):
+    """The wide sort's offsets in the container of ``data``; host results are
+    checked at the copy (-1: the failure convention), device results stay
+    asynchronous."""
+    if isinstance(data, torch.Tensor) and data.is_cuda:
+        return offsets
+    host = offsets.cpu()
+    if bool((host < 0).any()):
+        raise _lib.MgrError("the sorted cell ids are out of range or out of order (the device "
+                            "check of mgr_cell_offsets)")
+    return host if isinstance(data, torch.Tensor) else host.numpy()
+
+
+def ghost_grid(cell_length, cell_limits, fine_cells, overload_lengths, max_cells=GHOST_MAX_CELLS):
     """The extended fine grid of a rank's cell with ghost layers -- the single
     definition ``MPIGridRedistributor.ghost_grid`` / ``ghost_cell_sort`` and
     mgr_ghost_cells share (host numpy, no GPU).  ``cell_length[d]`` and
@@ -167,8 +287,15 @@ def ghost_grid(cell_length, cell_limits, fine_cells, overload_lengths):
 
     Cell k of dimension d covers [origin + (k - ghost) * width, origin + (k -
     ghost + 1) * width); cells ghost .. ghost + fine - 1 are the rank's own.
-    ValueError: prod(extents) beyond 1024 cells, a fine cell count < 1, a
-    negative or non-finite overload length."""
+    ``max_cells``: the bound on prod(extents) and on the ghost layers of a
+    dimension -- 1024 (GHOST_MAX_CELLS, the ranked sort) by default, up to
+    CELLS_MAX = 2^20 for the two-digit sort of ``ghost_cell_sort(...,
+    max_cells=)``.  ValueError: prod(extents) beyond ``max_cells``, a fine
+    cell count < 1, a negative or non-finite overload length, ``max_cells``
+    outside 1..CELLS_MAX."""
+    max_cells = int(max_cells)
+    if not 1 <= max_cells <= CELLS_MAX:
+        raise ValueError(f"max_cells {max_cells}: 1..{CELLS_MAX}")
     cl = np.asarray(cell_length, dtype=np.float64)
     fine = np.array(fine_cells).astype(np.int64)
     ol = np.asarray(overload_lengths, dtype=np.float64)
@@ -183,16 +310,17 @@ def ghost_grid(cell_length, cell_limits, fine_cells, overload_lengths):
     if not np.isfinite(width).all() or (width <= 0).any():
         raise ValueError(f"cell lengths {cl.tolist()}: positive and finite")
     ghost = np.where(ol == 0, 0.0, np.ceil(ol / width))
-    if (ghost > GHOST_MAX_CELLS).any():
-        raise ValueError(f"ghost layers of {ghost.tolist()} cells: beyond {GHOST_MAX_CELLS}")
+    if (ghost > max_cells).any():
+        raise ValueError(f"ghost layers of {ghost.tolist()} cells: beyond {max_cells}")
     ghost = ghost.astype(np.int64)
     extents = fine + 2 * ghost
     cells = 1
     for e in extents:
         cells *= int(e)
-    if cells > GHOST_MAX_CELLS:
+    if cells > max_cells:
+        why = ("the ranked sort's bound" if max_cells == GHOST_MAX_CELLS else "max_cells")
         raise ValueError(f"extended grid {extents.tolist()} has {cells} cells: at "
-                         f"most {GHOST_MAX_CELLS} (the ranked sort's bound); use fewer fine cells")
+                         f"most {max_cells} ({why}); use fewer fine cells")
     origin = np.ascontiguousarray(np.asarray(cell_limits, dtype=np.float64)[:, 0])
     return ghost, extents, origin, width
 
@@ -202,7 +330,9 @@ def _sort_by_cells(data, position, dim, dev, nb, cell_ids, return_positions, ret
     """What fine_cell_sort and ghost_cell_sort share: the payload's fields
     (and the position rows with ``return_positions``) stably sorted by the ids
     of ``cell_ids(pos, n, fields)`` -> (ids, check_ids, after); ``after(counts)``
-    (or None) runs before the counts become offsets.  Returns (data, [positions,]
+    (or None) runs before the counts become offsets.  int32 ids are 32-bit cell
+    ids (nb > 1024 cells): the two-digit sort (_sort_by_wide_ids), where
+    ``after`` gets the offsets.  Returns (data, [positions,]
     offsets[nb + 1], [SortRoute]).  ``floats``: the caller's name, if it takes
     float32 / float64 positions only; ``failed``: what -1 counts mean there."""
     rows, multi = _payload(data, dev)
@@ -215,8 +345,12 @@ def _sort_by_cells(data, position, dim, dev, nb, cell_ids, return_positions, ret
     prow = Rows(position, dev) if return_positions else None
     fields = rows + ([prow] if prow else [])
     ids, check, after = cell_ids(pos, n, fields)
-    outs, counts, *sroute = _sort_by_ids(fields, ids, n, nb, dev, check_ids=check,
-                                         route=return_route)
+    wide = ids.dtype == torch.int32
+    if wide:
+        outs, counts, *sroute = _sort_by_wide_ids(fields, ids, n, nb, dev, route=return_route)
+    else:
+        outs, counts, *sroute = _sort_by_ids(fields, ids, n, nb, dev, check_ids=check,
+                                             route=return_route)
     if after is not None:
         after(counts)
     nd = len(rows)
@@ -224,7 +358,8 @@ def _sort_by_cells(data, position, dim, dev, nb, cell_ids, return_positions, ret
     if prow:
         res.append(prow.wrap(outs[nd], n))
     try:
-        res.append(_offsets_like(rows[0].obj, counts, dev))
+        res.append(_wide_offsets_like(rows[0].obj, counts) if wide
+                   else _offsets_like(rows[0].obj, counts, dev))
     except _lib.MgrError as e:
         if failed is None:
             raise
