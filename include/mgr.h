@@ -17,6 +17,8 @@
  *   - everything that takes a stream is stream-ordered and asynchronous: no
  *     host synchronisation, no allocation (graph-capturable), except
  *     mgr_comm_* creation and the explicitly synchronous helpers noted below;
+ *     mgr_partition_onepass and mgr_partition_onepass_fields are stream-ordered
+ *     but must not be captured into a graph yet (see their comments);
  *   - workspaces are caller-owned device memory sized by mgr_workspace_bytes;
  *   - a plan is immutable after creation and may be shared by streams; one
  *     workspace must not be used by two in-flight calls at once.
@@ -362,6 +364,7 @@ int mgr_partition_by_position(const mgr_plan* plan, void* pos, int pos_dtype, in
  * reports every such tile; its completion counter measured +0.43 ms on this
  * kernel).  Workspace: mgr_onepass_workspace_bytes (zeroed by the call).
  * MGR_EUNSUPPORTED for shapes it does not take.
+ * Graph capture: not supported yet, as mgr_partition_onepass_fields below.
  * Tail read: the records are staged in 16-byte units from the 16-byte-aligned
  * data, so the last unit may READ up to 12 bytes past the array's end, inside
  * its aligned 16-byte unit (never written, never used).                    */
@@ -396,6 +399,9 @@ int mgr_partition_onepass(const mgr_plan* plan, const mgr_plan* fine_plan, void*
  *     may READ up to 12 bytes past the array's end, inside its aligned
  *     16-byte unit (never written, never used).
  * Workspace: mgr_onepass_workspace_bytes(n, nbins), zeroed by the call.
+ * Graph capture: not supported yet.  The capture succeeds, but a replay of the
+ *   captured call ended in an illegal memory access whose cause is not found;
+ *   call it eagerly on the stream (tests/test_gpu_stream_order.py).
  * MGR_EINVAL: a null plan / srcs / row_bytes / bin_counts, nfields outside
  * 1..MGR_MAX_FIELDS, pos_field out of range, n or cap_rows < 0, for n > 0 a
  * null source, workspace or output (other than the position field's), or

@@ -36,7 +36,7 @@ def synth_uniform(n, seed=20261015, gid0=0, dim=3, box=1.0, records=True, stream
     _lib.call("mgr_synth_uniform", ctypes.c_uint64(seed), int(gid0), int(n), int(dim),
               b.ctypes.data_as(ctypes.c_void_p), _lib.ptr(pos), _lib.ptr(rec),
               _lib.stream_handle(stream))
-    torch.cuda.current_stream().synchronize()
+    (stream if stream is not None else torch.cuda.current_stream()).synchronize()
     return pos, rec
 
 
